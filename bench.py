@@ -6,7 +6,7 @@ per-step API traffic of the reference rollout loop.  Workload:
 16x16 basesWorkers, 8192 envs per GPU (4096 selfplay games, random vs random),
 max_steps 2000, auto-reset on, inputs already resident in HBM.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
   N>1: either under a launcher (python -m torch.distributed.run --nproc-per-node N
        ... bench.py --gpus N: WORLD_SIZE must equal N), or plain `bench.py --gpus N`,
        which starts the N ranks itself as child processes (launch_ranks) before
@@ -16,12 +16,16 @@ Each rank owns an independent contiguous shard of envs (no data-path
 collective: envs never interact); the only communication is the timing
 barrier and the max-over-ranks of the elapsed time.
 
-Rank 0 prints one JSON line.  The timed region carries no HIP events;
-`roofline` prices the dominant kernel from a separate pass of --roofline-steps
-(>= 64) steps right after it, with HIP events around every launch of every step
-(`roofline.samples` launches); `cpu_baseline` times the CPU restatement
-(oracle/, OpenMP over games) on a bounded sample of the same workload (rank 0,
-N=1 only).
+Rank 0 prints one JSON line.  A plain run sets up, pre-rolls, warms up, times
+the K steps and prints the headline (`value`, `ms_per_step`, the window's
+statistics); --dump-outputs DIR also saves what the last timed step returned.
+The timed region carries no HIP events.  Everything that takes runs of its own
+is behind --full: `roofline` prices the dominant kernel from a separate pass of
+--roofline-steps (>= 64) steps right after the timed window, with HIP events
+around every launch of every step (`roofline.samples` launches), next to the
+GPU's measured write ceiling (`window.box_write_ceiling`); `cpu_baseline` times the
+CPU restatement (oracle/, OpenMP over games) on a bounded sample of the same
+workload (rank 0, N=1 only).
 """
 import argparse
 import json
@@ -48,10 +52,18 @@ def parse(argv=None):
     ap.add_argument("--seeds", type=int, default=1,
                     help="independent runs with seeds seed, seed+1, ... (fresh env, pre-roll, warmup and K timed steps "
                          "each); the line reports the median run (BASELINE.md §3: median of 3 seeds) and every seed's value")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed window also run the secondary measurements: the event-timed roofline pass "
+                         "(roofline / kernels / window.box_write_ceiling) and the CPU baseline (cpu_baseline); a plain "
+                         "run times the steps and prints the headline only")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps save what the last one returned (obs, reward, done), the actions it "
+                         "was given and the action-mask buffer after it as float32 DIR/<name>.npy (rank 0; a fixed "
+                         "seeded sample of envs, listed in envs.npy, when all of them would exceed DUMP_BUDGET)")
     ap.add_argument("--cpu-baseline-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--no-kernel-events", action="store_true",
-                    help="skip the event-timed roofline pass (no roofline / kernels in the line)")
+                    help="--full without the event-timed roofline pass (no roofline / kernels in the line)")
     ap.add_argument("--roofline-steps", type=int, default=64,
                     help="steps of the event-timed pass after the timed window (HIP events around every launch)")
     ap.add_argument("--bot-fusion", type=int, default=1, choices=[0, 1],
@@ -175,13 +187,41 @@ def roofline_pass(args, one_step, timing, s1):
     HIP events around every launch of every step."""
     import torch
 
-    if args.no_kernel_events or args.roofline_steps <= 0:
+    if not args.full or args.no_kernel_events or args.roofline_steps <= 0:
         return
     timing[0] = True
     for s in range(s1, s1 + args.roofline_steps):
         one_step(s)
     torch.cuda.synchronize()
     timing[0] = False
+
+
+# --dump-outputs: bytes of float32 arrays one run may write (the files stay under 64 MB in all)
+DUMP_BUDGET = 48 << 20
+
+
+def dump_outputs(path, outputs, suffix="", budget=DUMP_BUDGET):
+    """--dump-outputs: save `outputs` = {name: array or device tensor, first axis =
+    env} as float32 <path>/<name><suffix>.npy.  When all envs would take more than
+    `budget` bytes, every array keeps the same sample of envs: a seeded choice
+    without replacement (the same for the same env count), sorted, saved as
+    envs<suffix>.npy next to them."""
+    import numpy as np
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    n = len(next(iter(outputs.values())))
+    per_env = sum(4 * (int(np.prod(v.shape[1:])) if len(v.shape) > 1 else 1) for v in outputs.values())
+    keep = max(1, min(n, budget // per_env))
+    idx = np.arange(n) if keep == n else np.sort(np.random.default_rng(2024).choice(n, keep, replace=False))
+    np.save(os.path.join(path, f"envs{suffix}.npy"), idx.astype(np.float64))
+    for name, v in outputs.items():
+        assert len(v) == n, (name, len(v), n)
+        if isinstance(v, torch.Tensor):
+            v = v[torch.as_tensor(idx, device=v.device)].cpu().numpy()
+        else:
+            v = np.asarray(v)[idx]
+        np.save(os.path.join(path, f"{name}{suffix}.npy"), np.ascontiguousarray(v, dtype=np.float32))
 
 
 def run_mixed(args, rank, world, dev):
@@ -256,11 +296,15 @@ def run_mixed(args, rank, world, dev):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for s in range(s0 + args.warmup, s0 + args.warmup + args.steps):
-        one_step(s)
+        out = one_step(s)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     barrier(world, dev)
     after = [e.game_stats() for e in env.envs]
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        for b, e in enumerate(env.envs):   # one set of files per size bucket
+            dump_outputs(args.dump_outputs, {"obs": out[0][b], "reward": out[1][b], "done": out[2][b], "actions": acts[b],
+                                             "action_mask": e._mask}, f"_bucket{b}", DUMP_BUDGET // len(env.envs))
     roofline_pass(args, one_step, timing, s0 + args.warmup + args.steps)
     for e in env.envs:
         e.kernel_events = None
@@ -460,6 +504,8 @@ def run_gpu(args, rank, world, local_rank):
         np.savez(f"{args.dump}.rank{rank}.npz", obs=obs.cpu().numpy(), mask=env._mask.cpu().numpy(),
                  src=env._src.cpu().numpy(), raw=env._raw.cpu().numpy(), done=env._done.cpu().numpy(),
                  stats=env.game_stats(), env0=env0)
+    if args.dump_outputs and rank == 0 and args.steps > 0:
+        dump_outputs(args.dump_outputs, {"obs": obs, "reward": rew, "done": done, "actions": act, "action_mask": env._mask})
     roofline_pass(args, one_step, timing, s0 + args.warmup + args.steps)
     env.kernel_events = None
     stats["roofline_samples"] = len(ev.get("step", []))
@@ -467,7 +513,7 @@ def run_gpu(args, rank, world, local_rank):
     kern = {k: float(np.mean([a.elapsed_time(b) for a, b in v])) for k, v in ev.items()}  # ms per launch
     G = nsp // 2 + nbot
     src_rows = int(env._src.sum().item())   # source cells of the last step (sampler bytes)
-    if not args.no_kernel_events and rank == 0:
+    if args.full and not args.no_kernel_events and rank == 0:
         stats["box_write_ceiling"] = write_ceiling(dev, kernel_bytes(G, n, hw, sum(env.num_planes))["step"])
     return elapsed, kern, flags, env.height * env.width, G, env.num_envs, sum(env.num_planes), src_rows, stats
 
@@ -731,6 +777,8 @@ def main(argv=None):
         for i in range(max(1, args.seeds)):
             a = argparse.Namespace(**vars(args))
             a.seed = args.seed + i
+            if i:
+                a.dump_outputs = None   # --dump-outputs: the first seed's run
             runs.append((a.seed, run_gpu(a, rank, world, local_rank)))
         order = sorted(range(len(runs)), key=lambda i: runs[i][1][0])
         elapsed, kern, flags, hw, G, N, P, src_rows, stats = runs[order[len(order) // 2]][1]
@@ -838,7 +886,7 @@ def main(argv=None):
             out["config"]["api"] = args.api
             out["metric"] = ("env-steps/sec, reference numpy contract (obs / masks / rewards copied to the host, host "
                              "actions in: PCIe-inclusive; not the headline)")
-        if world == 1 and not args.no_cpu_baseline and args.workload in CPU_WORKLOADS:
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload in CPU_WORKLOADS:
             out["cpu_baseline"] = cpu_baseline(args.cpu_baseline_seconds, workload=args.workload)
         print(json.dumps(out), flush=True)
     if world > 1:

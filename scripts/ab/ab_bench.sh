@@ -15,7 +15,7 @@ for r in $(seq 1 "$R"); do
   for v in "$@"; do
     n=$(basename "$v" .so)
     if [ "$v" = cur ]; then cp "$O/.cur.so" "$L"; else cp "$v" "$L"; fi
-    timeout -k 10 300 python bench.py $ARGS --no-cpu-baseline > "$O/${n}_r$r.json" 2> "$O/${n}_r$r.err"
+    timeout -k 10 300 python bench.py --full $ARGS --no-cpu-baseline > "$O/${n}_r$r.json" 2> "$O/${n}_r$r.err"
     python -c "import json,sys; d=json.loads(open(sys.argv[1]).read().strip().splitlines()[-1]); r=d.get('roofline') or {}; print(sys.argv[2], sys.argv[3], round(d['value']/1e6,3), 'M', r.get('avg_launch_ms'), r.get('frac'))" "$O/${n}_r$r.json" "$n" "$r"
   done
 done

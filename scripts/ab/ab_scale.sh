@@ -10,10 +10,10 @@ for round in $(seq 1 $3); do
     cp scripts/ab/lib$v.so $L
     line="$v $round"
     for n in 512 2048 8192; do
-      timeout -k 10 200 python bench.py --no-cpu-baseline --steps 150 --envs-per-gpu $n > $O/head_${v}_$n.$round.json 2>/dev/null
+      timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 150 --envs-per-gpu $n > $O/head_${v}_$n.$round.json 2>/dev/null
       line="$line | $n: $(python -c "import json; d=json.load(open('$O/head_${v}_$n.$round.json')); print(round(d['kernels']['step']['avg_ms']*1000,1))")"
     done
-    timeout -k 10 200 python bench.py --workload coac --envs-per-gpu 1024 --no-cpu-baseline --steps 300 > $O/coac_$v.$round.json 2>/dev/null
+    timeout -k 10 200 python bench.py --full --workload coac --envs-per-gpu 1024 --no-cpu-baseline --steps 300 > $O/coac_$v.$round.json 2>/dev/null
     line="$line | coac1024: $(python -c "import json; d=json.load(open('$O/coac_$v.$round.json')); print(round(d['kernels']['step']['avg_ms']*1000,1))")"
     echo "$line"
   done

@@ -11,7 +11,7 @@ for round in $(seq 1 $3); do
     line="$v $round"
     for wl in $4; do
       w=${wl%%:*}; n=${wl##*:}
-      timeout -k 10 200 python bench.py --no-cpu-baseline --steps 150 --workload $w --envs-per-gpu $n > $O/${v}_${w}_$n.$round.json 2>/dev/null
+      timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 150 --workload $w --envs-per-gpu $n > $O/${v}_${w}_$n.$round.json 2>/dev/null
       line="$line | $w@$n: $(python -c "import json; d=json.load(open('$O/${v}_${w}_$n.$round.json')); print(d['value'], round(d['roofline']['avg_launch_ms']*1000,1))")"
     done
     echo "$line"

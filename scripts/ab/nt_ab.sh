@@ -13,8 +13,8 @@ echo "parity $3: $(tail -1 $O/parity_$3.txt)"
 for round in 1 2; do
   for v in $2; do
     cp scripts/ab/lib$v.so $L
-    timeout -k 10 300 python bench.py --workload mixed --no-cpu-baseline --steps 200 --warmup 30 > $O/mixed_$v.$round.json 2>/dev/null
-    timeout -k 10 300 python bench.py --workload 24x24 --no-cpu-baseline --steps 100 --warmup 20 > $O/s24_$v.$round.json 2>/dev/null
+    timeout -k 10 300 python bench.py --full --workload mixed --no-cpu-baseline --steps 200 --warmup 30 > $O/mixed_$v.$round.json 2>/dev/null
+    timeout -k 10 300 python bench.py --full --workload 24x24 --no-cpu-baseline --steps 100 --warmup 20 > $O/s24_$v.$round.json 2>/dev/null
     python - $O/mixed_$v.$round.json $O/s24_$v.$round.json $v $round <<'PY'
 import json, sys
 m = json.load(open(sys.argv[1])); s = json.load(open(sys.argv[2]))

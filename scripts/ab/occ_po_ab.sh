@@ -15,7 +15,7 @@ for r in 1 2; do
     cp scripts/ab/lib$v.so $L
     for spec in "partial_obs 4096" "partial_obs 8192" "selfplay 8192" "coac 1024"; do
       set -- $spec
-      timeout -k 10 300 python bench.py --workload $1 --envs-per-gpu $2 --steps 200 --warmup 30 --no-cpu-baseline > $O/${1}_$2_$v.$r.json 2>/dev/null
+      timeout -k 10 300 python bench.py --full --workload $1 --envs-per-gpu $2 --steps 200 --warmup 30 --no-cpu-baseline > $O/${1}_$2_$v.$r.json 2>/dev/null
       python -c "import json; d=json.load(open('$O/${1}_$2_$v.$r.json')); print('$v r$r $1@$2', round(d['value']/1e6,2), round(d['kernels']['step']['avg_ms']*1000,1))"
     done
   done

@@ -11,7 +11,7 @@ for m in 1 2 3; do
 done
 for r in 1 2; do
   for m in 0 1 2 3; do
-    MRTS_EXP_ORDER=$m timeout -k 10 300 python bench.py --workload mixed --no-cpu-baseline --steps 200 --warmup 30 > $O/mixed_$m.$r.json 2>/dev/null
+    MRTS_EXP_ORDER=$m timeout -k 10 300 python bench.py --full --workload mixed --no-cpu-baseline --steps 200 --warmup 30 > $O/mixed_$m.$r.json 2>/dev/null
     python -c "import json; d=json.load(open('$O/mixed_$m.$r.json')); print('order $m r$r', round(d['value']/1e6,2), d['roofline']['avg_launch_ms'])"
   done
 done

@@ -17,8 +17,8 @@ done
 for round in $(seq 1 ${3:-2}); do
   for v in $2; do
     cp scripts/ab/lib$v.so $L
-    timeout -k 10 200 python bench.py --no-cpu-baseline --steps 150 > $O/head_$v.$round.json 2>/dev/null
-    timeout -k 10 200 python bench.py --workload coac --envs-per-gpu 1024 --no-cpu-baseline --steps 300 > $O/coac_$v.$round.json 2>/dev/null
+    timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 150 > $O/head_$v.$round.json 2>/dev/null
+    timeout -k 10 200 python bench.py --full --workload coac --envs-per-gpu 1024 --no-cpu-baseline --steps 300 > $O/coac_$v.$round.json 2>/dev/null
     python - $O/head_$v.$round.json $O/coac_$v.$round.json $v $round <<'PY'
 import json, sys
 out = []

@@ -11,7 +11,7 @@ cp scripts/ab/libsplit.so $L
 MRTS_EXP_SPLIT=512 timeout -k 10 300 python -m pytest tests/test_gpu_fullsize.py -m gpu -q -k "selfplay_8192" > $O/parity.txt 2>&1 && echo "parity ok" || { echo "parity FAIL"; tail -5 $O/parity.txt; }
 for round in 1 2; do
   for K in 0 256 512 1024 1536; do
-    MRTS_EXP_SPLIT=$K timeout -k 10 200 python bench.py --no-cpu-baseline --steps 200 > $O/head_$K.$round.json 2>/dev/null
+    MRTS_EXP_SPLIT=$K timeout -k 10 200 python bench.py --full --no-cpu-baseline --steps 200 > $O/head_$K.$round.json 2>/dev/null
     python -c "import json; d=json.load(open('$O/head_$K.$round.json')); print('K=$K r$round', round(d['value']/1e6,2), round(d['kernels']['step']['avg_ms']*1000,1))"
   done
 done

@@ -16,6 +16,6 @@ if [ -n "$K" ]; then
 fi
 for w in "coac 1024" "coac 8192" "workerrush 8192"; do
   set -- $w
-  timeout -k 10 200 python bench.py --workload $1 --envs-per-gpu $2 --no-cpu-baseline > "$O/${1}_$2.json" 2>> "$O/bench.err"
+  timeout -k 10 200 python bench.py --full --workload $1 --envs-per-gpu $2 --no-cpu-baseline > "$O/${1}_$2.json" 2>> "$O/bench.err"
   python -c "import json,sys; d=json.load(open('$O/${1}_$2.json')); print('$1', $2, round(d['value']/1e6,2), 'M/s', 'step', d['kernels']['step']['avg_ms'], 'frac', d['roofline']['frac'])"
 done

@@ -10,6 +10,6 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_bots.py tests/test_gpu_full
 tail -2 "$O/pytest.log"
 for spec in "coac 1024" "coac 8192" "workerrush 8192" "mixed 8192"; do
   set -- $spec
-  timeout -k 10 300 python bench.py --workload "$1" --envs-per-gpu "$2" --steps 200 --warmup 30 --no-cpu-baseline > "$O/$1_$2.json" 2> "$O/$1_$2.err"
+  timeout -k 10 300 python bench.py --full --workload "$1" --envs-per-gpu "$2" --steps 200 --warmup 30 --no-cpu-baseline > "$O/$1_$2.json" 2> "$O/$1_$2.err"
 done
 for f in "$O"/*.json; do python -c "import json,sys; d=json.load(open(sys.argv[1])); print(sys.argv[1].split('/')[-1], round(d['value']/1e6,2), 'M', {k:round(v['avg_ms']*1e3,1) for k,v in d.get('kernels',{}).items()})" "$f"; done

@@ -14,7 +14,7 @@ timeout -k 10 600 python -u -m pytest tests/test_gpu_bots.py -m gpu -x -v --time
 tail -2 "$O/pytest.log"
 for r in $(seq 1 "$ROUNDS"); do
   for pol in none 0 1 5 2 6; do
-    timeout -k 10 300 python bench.py --workload mixed --steps 200 --warmup 30 --group-policy "$pol" > "$O/mixed_${pol}_r$r.json" 2> "$O/mixed_${pol}_r$r.err"
+    timeout -k 10 300 python bench.py --full --workload mixed --steps 200 --warmup 30 --group-policy "$pol" > "$O/mixed_${pol}_r$r.json" 2> "$O/mixed_${pol}_r$r.err"
     python - "$O/mixed_${pol}_r$r.json" "$pol" "$r" <<'PY'
 import json, sys
 d = json.loads(open(sys.argv[1]).read().strip().splitlines()[-1])

@@ -17,9 +17,9 @@ if [ "${SKIP_TESTS:-0}" != 1 ]; then
     || { echo "pytest failed"; tail -40 "$O/pytest_gpu.log"; exit 1; }
   tail -2 "$O/pytest_gpu.log"
 fi
-BENCH="bench.py --steps 100 --warmup 20 --no-cpu-baseline"
-COAC="bench.py --workload coac --envs-per-gpu 1024 --steps 300 --warmup 20 --no-cpu-baseline"
-MIXED="bench.py --workload mixed --steps 100 --warmup 20 --no-cpu-baseline"
+BENCH="bench.py --full --steps 100 --warmup 20 --no-cpu-baseline"
+COAC="bench.py --full --workload coac --envs-per-gpu 1024 --steps 300 --warmup 20 --no-cpu-baseline"
+MIXED="bench.py --full --workload mixed --steps 100 --warmup 20 --no-cpu-baseline"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$O/kt" -o kt -- python3 $BENCH > "$O/bench_kt.json" 2> "$O/kt.err"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$O/kt_coac" -o kt -- python3 $COAC > "$O/bench_coac_kt.json" 2> "$O/kt_coac.err"
 timeout -k 10 300 rocprofv3 --kernel-trace --stats -f csv -d "$O/kt_mixed" -o kt -- python3 $MIXED > "$O/bench_mixed_kt.json" 2> "$O/kt_mixed.err"
@@ -34,8 +34,8 @@ for W in selfplay coac mixed; do
   python3 scripts/pmc_summary.py "$O/pmc_$W" "$O/pmc_latest.json" --workload $KEY --command "$CMD" > "$O/pmc_$W.txt"
 done
 cp "$O/pmc_latest.json" profiles/pmc_latest.json
-timeout -k 10 300 python bench.py > "$O/bench.json" 2> "$O/bench.err"
-timeout -k 10 300 python bench.py --workload coac --envs-per-gpu 1024 --no-cpu-baseline > "$O/bench_coac.json" 2> "$O/bench_coac.err"
-timeout -k 10 300 python bench.py --workload mixed --no-cpu-baseline > "$O/bench_mixed.json" 2> "$O/bench_mixed.err"
+timeout -k 10 300 python bench.py --full > "$O/bench.json" 2> "$O/bench.err"
+timeout -k 10 300 python bench.py --full --workload coac --envs-per-gpu 1024 --no-cpu-baseline > "$O/bench_coac.json" 2> "$O/bench_coac.err"
+timeout -k 10 300 python bench.py --full --workload mixed --no-cpu-baseline > "$O/bench_mixed.json" 2> "$O/bench_mixed.err"
 cat "$O/bench.json" "$O/bench_coac.json" "$O/bench_mixed.json"
 echo done > "$O/DONE"

@@ -18,7 +18,7 @@ i=0
 IFS=';' read -ra B <<< "${BENCHES:-}"
 for args in "${B[@]}"; do
   [ -z "$args" ] && continue
-  timeout -k 10 ${BENCH_TIMEOUT:-300} python bench.py $args > "$O/bench_$i.json" 2> "$O/bench_$i.err"
+  timeout -k 10 ${BENCH_TIMEOUT:-300} python bench.py --full $args > "$O/bench_$i.json" 2> "$O/bench_$i.err"
   echo "bench $i ($args): $(python -c "import json,sys; d=json.load(open('$O/bench_$i.json')); print(d['value'], d['ms_per_step'], (d.get('roofline') or {}).get('frac'), (d.get('cpu_baseline') or {}).get('value'))")"
   i=$((i+1))
 done

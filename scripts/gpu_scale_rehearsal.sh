@@ -11,8 +11,8 @@ O=gpurun_out/$TAG
 mkdir -p "$O"
 PORT=$(python -c "import socket; s=socket.socket(); s.bind(('127.0.0.1',0)); print(s.getsockname()[1])")
 timeout -k 10 600 python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port "$PORT" \
-  bench.py --gpus 8 --steps 50 --warmup 10 > "$O/torchrun_8.json" 2> "$O/torchrun_8.err"
-timeout -k 10 600 python bench.py --gpus 4 --steps 50 --warmup 10 > "$O/self_4.json" 2> "$O/self_4.err"
+  bench.py --full --gpus 8 --steps 50 --warmup 10 > "$O/torchrun_8.json" 2> "$O/torchrun_8.err"
+timeout -k 10 600 python bench.py --full --gpus 4 --steps 50 --warmup 10 > "$O/self_4.json" 2> "$O/self_4.err"
 python - "$O" <<'PY'
 import glob, json, os, sys
 for f in sorted(glob.glob(os.path.join(sys.argv[1], "*.json"))):

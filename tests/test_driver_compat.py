@@ -2,11 +2,12 @@
 wrappers, torch.utils.tensorboard; experiments/ppo_gridnet.py:17-20) resolved by
 gym_microrts.run_driver's stand-ins.
 
-CPU: the stand-ins' semantics on a host-only VecEnv, and -- in the container that
-holds the reference -- the unmodified ppo_gridnet.py importing through them.
+CPU: the stand-ins' semantics on a host-only VecEnv, and the recorded module-level
+imports of ppo_gridnet.py and its siblings resolving through them.
 GPU: ppo_gridnet.py's wrapper stack (VecEnvWrapper subclass -> VecMonitor) over
 MicroRTSGridModeVecEnv, with episodes ending at max_steps.
 """
+import json
 import os
 import subprocess
 import sys
@@ -16,7 +17,7 @@ import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PKG = os.path.join(REPO, "microrts-py_amd")
-REF_PPO = "/root/reference/experiments/ppo_gridnet.py"
+DRIVER_IMPORTS = os.path.join(REPO, "tests", "golden", "reference_driver_imports.json")
 
 
 @pytest.fixture(scope="module")
@@ -131,16 +132,22 @@ def test_video_recorder_writes_frames(compat, tmp_path):
     assert np.load(tmp_path / clip)["frames"][:, 0, 0, 0].tolist() == [0, 1, 2]
 
 
-@pytest.mark.skipif(not os.path.exists(REF_PPO), reason="reference checkout only in the build container")
 @pytest.mark.parametrize("script,flag", [("ppo_gridnet.py", "--num-selfplay-envs"), ("ppo_gridnet_eval.py", "--model-type"),
                                          ("ppo_gridnet_large.py", "--num-selfplay-envs")])
 def test_reference_drivers_import_unmodified(tmp_path, script, flag):
-    """The unmodified experiments/ drivers get through every import
-    (gym, stable_baselines3, torch.utils.tensorboard, gym_microrts = this package) and their
-    argument parsers under the runner (the env itself needs the GPU)."""
+    """The experiments/ drivers get through every module-level import
+    (gym, stable_baselines3, torch.utils.tensorboard, gym_microrts = this package) and an
+    argument parser under the runner (the env itself needs the GPU).  The drivers are not
+    part of this repository: tests/golden/reference_driver_imports.json records their
+    module-level imports, name for name, and the probe written here makes exactly those."""
+    rec = json.load(open(DRIVER_IMPORTS))["drivers"][script]
+    assert rec["flag"] == flag
+    lines = [f"from {mod} import {', '.join(names)}" if names else f"import {mod}" for mod, names in rec["imports"]]
+    lines += ["p = argparse.ArgumentParser()", f"p.add_argument({flag!r}, type=int, default=1)", "p.parse_args()"]
+    path = tmp_path / script
+    path.write_text("\n".join(lines) + "\n")
     env = dict(os.environ, PYTHONPATH=PKG)
-    path = os.path.join(os.path.dirname(REF_PPO), script)
-    p = subprocess.run([sys.executable, "-m", "gym_microrts.run_driver", path, "--help"], cwd=tmp_path, env=env,
+    p = subprocess.run([sys.executable, "-m", "gym_microrts.run_driver", str(path), "--help"], cwd=tmp_path, env=env,
                        capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
     assert flag in p.stdout

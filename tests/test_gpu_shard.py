@@ -112,7 +112,7 @@ def test_bench_sharding_end_to_end(tmp_path, launcher, world):
     `bench.py --gpus N`, which starts its ranks itself (bench.launch_ranks).  The line
     carries one per-rank entry per rank (window.per_rank)."""
     total = 512
-    common = ["--steps", "25", "--warmup", "3", "--preroll", "120", "--max-steps", "120", "--no-cpu-baseline",
+    common = ["--steps", "25", "--warmup", "3", "--preroll", "120", "--max-steps", "120", "--full", "--no-cpu-baseline",
               "--roofline-steps", "8", "--rank-timeout", "240"]
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
