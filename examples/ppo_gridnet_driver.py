@@ -18,6 +18,11 @@ envs) runs end to end on the GPU.
                  obs / masks stay device tensors, rewards / dones / infos numpy
   --api tensor : return_tensors=True, every buffer stays in HBM
 
+  --head torch : the masked categorical head in torch ops (`policy()` below), the default
+  --head fused : gym_microrts.policy_head -- the head as HIP kernels that read only the
+                 rows of cells holding a unit that can act (sample in the rollout,
+                 evaluate + its backward in the update); --api tensor only
+
 With --api numpy / hybrid the rollout makes ppo_gridnet.py's own calls in its own
 forms (`torch.Tensor(envs.reset()).to(device)`, `torch.tensor(envs.get_action_mask())
 .to(device)`, `envs.step(action.cpu().numpy().reshape(n, -1))`, `torch.Tensor(rs)`,
@@ -46,7 +51,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "microrts-py_amd"))
 
-from gym_microrts import microrts_ai  # noqa: E402
+from gym_microrts import microrts_ai, policy_head  # noqa: E402
 from gym_microrts.envs.vec_env import MicroRTSGridModeVecEnv  # noqa: E402
 from gym_microrts.run_driver import install as _install_compat  # noqa: E402
 
@@ -191,6 +196,19 @@ def policy(net, obs, mask, hw, action=None):
     return a.reshape(-1, hw, len(NVEC)), logp.reshape(-1, hw).sum(1), ent.reshape(-1, hw).sum(1), value
 
 
+def policy_fused(net, obs, mask, source, action=None, seed=0, step=0):
+    """policy() over gym_microrts.policy_head: mask / source are the engine's int32
+    tensors (or the rollout buffer's copies of them).  A component without a valid
+    entry contributes 0 to the log-prob and the entropy (the reference's float32
+    result), where policy()'s log_softmax gives -log(len) and log(len)."""
+    logits, value = net(obs)
+    if action is None:
+        action, logp, ent = policy_head.sample(logits, mask, source, seed=seed, step=step)
+    else:
+        logp, ent = policy_head.evaluate(logits, mask, source, action)
+    return action, logp, ent, value
+
+
 def bot_list(n):
     """ppo_gridnet.py:370-373's opponents (n >= 6 bot envs)."""
     return ([microrts_ai.coacAI] * (n - 6) + [microrts_ai.randomBiasedAI] * min(n, 2) + [microrts_ai.lightRushAI] * min(n, 2)
@@ -198,7 +216,15 @@ def bot_list(n):
 
 
 def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, updates=2, api="numpy", minibatches=4,
-        epochs=2, seed=1, device="cuda", log=print, max_steps=2000):
+        epochs=2, seed=1, device="cuda", log=print, max_steps=2000, head="torch", keep_first_rollout=False):
+    """head: "torch" or "fused" (policy_fused; --api tensor only).  keep_first_rollout: the
+    returned stats carry "first_rollout" -- the first rollout's buffers and the weights
+    that acted in it."""
+    if head not in ("torch", "fused"):
+        raise ValueError(f"head must be 'torch' or 'fused', not {head!r}")
+    if head == "fused" and api != "tensor":
+        raise ValueError("--head fused needs --api tensor: the head reads the engine's device masks")
+    fused = head == "fused"
     torch.manual_seed(seed)
     np.random.seed(seed)
     dev = torch.device(device)
@@ -226,7 +252,9 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
     net = GridNet(planes, h, w).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=2.5e-4, eps=1e-5)
     buf_obs = torch.zeros((num_steps, n, h, w, planes), device=dev)
-    buf_mask = torch.zeros((num_steps, n, hw, sum(NVEC)), device=dev)
+    # the fused head reads the engine's int32 masks, and the source channel next to them
+    buf_mask = torch.zeros((num_steps, n, hw, sum(NVEC)), device=dev, dtype=torch.int32 if fused else torch.float32)
+    buf_src = torch.zeros((num_steps, n, hw), device=dev, dtype=torch.int32) if fused else None
     buf_act = torch.zeros((num_steps, n, hw, len(NVEC)), dtype=torch.long, device=dev)
     buf_logp, buf_rew, buf_done, buf_val = (torch.zeros((num_steps, n), device=dev) for _ in range(4))
 
@@ -238,16 +266,24 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
     ep_ret, finished = torch.zeros(n, device=dev), []
     steps, t0, stats, stats_seen = 0, time.time(), {}, 0
     rollout_s = 0.0
+    first_rollout = None
     for update in range(updates):
+        if keep_first_rollout and update == 0:
+            first_rollout = {"state_dict": {k: v.detach().clone() for k, v in net.state_dict().items()}}
         tr = time.time()
         for t in range(num_steps):
             buf_obs[t], buf_done[t] = next_obs, next_done
             with torch.no_grad():
                 if ref_calls:   # ppo_gridnet.py:466
                     buf_mask[t] = torch.tensor(envs.get_action_mask()).to(dev)
+                elif fused:
+                    buf_mask[t], buf_src[t] = envs.get_action_mask(), envs.source_unit_mask
                 else:
                     buf_mask[t] = as_dev(envs.get_action_mask())
-                a, logp, _, v = policy(net, next_obs, buf_mask[t], hw)
+                if fused:
+                    a, logp, _, v = policy_fused(net, next_obs, buf_mask[t], buf_src[t], seed=seed, step=update * num_steps + t)
+                else:
+                    a, logp, _, v = policy(net, next_obs, buf_mask[t], hw)
             buf_act[t], buf_logp[t], buf_val[t] = a, logp, v
             if ref_calls:   # ppo_gridnet.py:475-490: host int64 actions (N, H*W*7), numpy rewards / dones, info scan
                 obs, rs, ds, infos = envs.step(a.cpu().numpy().reshape(n, -1))
@@ -268,6 +304,9 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
             steps += n
         torch.cuda.synchronize(dev)
         rollout_s += time.time() - tr
+        if keep_first_rollout and update == 0:
+            first_rollout.update(obs=buf_obs.clone(), mask=buf_mask.clone(), actions=buf_act.clone(), logprob=buf_logp.clone(),
+                                 source=buf_src.clone() if fused else None)
         with torch.no_grad():   # GAE (gamma 0.99, lambda 0.95)
             _, last_v = net(next_obs)
             adv = torch.zeros_like(buf_rew)
@@ -280,6 +319,7 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
             ret = adv + buf_val
         B = num_steps * n
         flat = [x.reshape((B,) + x.shape[2:]) for x in (buf_obs, buf_mask, buf_act, buf_logp, adv, ret, buf_val)]
+        flat_src = buf_src.reshape(B, hw) if fused else None
         mb = max(1, B // minibatches)
         for _ in range(epochs):
             perm = torch.randperm(B, device=dev)
@@ -287,7 +327,10 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
                 idx = perm[s:s + mb]
                 o, m, a, lp0, ad, rt, v0 = (x[idx] for x in flat)
                 ad = (ad - ad.mean()) / (ad.std() + 1e-8)
-                _, lp, ent, v = policy(net, o, m, hw, action=a)
+                if fused:
+                    _, lp, ent, v = policy_fused(net, o, m, flat_src[idx], action=a)
+                else:
+                    _, lp, ent, v = policy(net, o, m, hw, action=a)
                 ratio = (lp - lp0).exp()
                 pg = torch.max(-ad * ratio, -ad * ratio.clamp(0.9, 1.1)).mean()
                 vc = v0 + (v - v0).clamp(-0.1, 0.1)
@@ -301,11 +344,13 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
         stats = {"update": update + 1, "global_step": steps, "sps": round(steps / (time.time() - t0), 1),
                  "rollout_env_steps_per_s": round(steps / rollout_s, 1), "loss": float(loss.detach()), "policy_loss": float(pg.detach()),
                  "value_loss": float(vl.detach()), "entropy": float(ent.detach().mean()), "episodes": len(finished),
-                 "microrts_stats_infos": stats_seen, "api": api, "num_envs": n, "partial_obs": bool(partial_obs)}
+                 "microrts_stats_infos": stats_seen, "api": api, "num_envs": n, "partial_obs": bool(partial_obs), "head": head}
         log(stats)
     stats["engine_error_flags"] = base.error_flags()
     stats["finite"] = bool(np.isfinite([stats["loss"], stats["value_loss"], stats["entropy"]]).all())
     envs.close()
+    if first_rollout is not None:
+        stats["first_rollout"] = first_rollout
     return stats
 
 
@@ -405,7 +450,8 @@ if __name__ == "__main__":
     ap.add_argument("--minibatches", type=int, default=4)
     ap.add_argument("--api", choices=["numpy", "hybrid", "tensor"], default="numpy")
     ap.add_argument("--max-steps", type=int, default=2000)
+    ap.add_argument("--head", choices=["torch", "fused"], default="torch")
     a = ap.parse_args()
     out = run(a.num_selfplay_envs, a.num_bot_envs, a.partial_obs, a.num_steps, a.updates, a.api, a.minibatches,
-              log=lambda s: print(json.dumps(s), flush=True), max_steps=a.max_steps)
+              log=lambda s: print(json.dumps(s), flush=True), max_steps=a.max_steps, head=a.head)
     print(json.dumps(out))

@@ -237,6 +237,39 @@ typedef struct mrts_sample_seg {
 } mrts_sample_seg;
 int mrts_sample_actions_src_group(void *stream, const mrts_sample_seg *segs, int32_t nseg, uint64_t seed, uint32_t step);
 
+/* The masked action head of a GridNet policy on the device: CategoricalMasked per
+ * action component and Agent.get_action_and_value's action is None branch
+ * (/root/reference/experiments/ppo_gridnet.py:164-167, 225-232, 241-247).
+ * logits [num_envs][hw][78] float32; mask / source as mrts_get_masks writes them
+ * (only the mask and logit rows of source cells are read).  Writes actions
+ * [num_envs][hw][7] int64 (what mrts_step takes; a non-source row gets the
+ * no-valid-entry draw of mrts_sample_actions_src), and per env the summed log-prob
+ * and entropy, logprob / entropy [num_envs] float32.  Per component with valid
+ * entries: the float32 softmax over them, sampled by inverse CDF from the Philox
+ * words of mrts_sample_actions_src (seed, counter = (cell, env0 + env, step):
+ * exact under sharding); a component without valid entries contributes 0 to both
+ * sums (the reference's float32 result for its -1e8 mask value).  Runs on `stream`,
+ * allocates and synchronises nothing.  MRTS_EINVAL before any launch: a null
+ * pointer, hw < 1, num_envs < 0, env0 < 0, num_envs * hw beyond 2^31 - 256. */
+int mrts_policy_sample(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t num_envs,
+                       int32_t hw, int32_t env0, uint64_t seed, uint32_t step, int64_t *actions, float *logprob, float *entropy);
+
+/* Agent.get_action_and_value with given actions (ppo_gridnet.py:233-247, the PPO
+ * update's call): logprob / entropy [num_envs] float32 of `actions` under the same
+ * masked softmax.  An action the mask forbids, or one outside its component's range,
+ * contributes exactly -1e8 (the reference's float32 value) and is never used as an
+ * index.  The same checks and stream rules as mrts_policy_sample. */
+int mrts_policy_evaluate(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t num_envs,
+                         int32_t hw, const int64_t *actions, float *logprob, float *entropy);
+
+/* What autograd derives for ppo_gridnet.py:241-247 (loss.backward() at :566): given
+ * grad_logprob / grad_entropy [num_envs] float32, writes ALL of grad_logits
+ * [num_envs][hw][78] float32 (no pre-zeroing): the softmax gradient on valid entries,
+ * +0.0f on masked entries, components without valid entries and non-source rows. */
+int mrts_policy_evaluate_backward(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t num_envs,
+                                  int32_t hw, const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
+                                  float *grad_logits);
+
 /* Per-game rollout statistics, host int32 out[num_games][MRTS_GAME_STATS]:
  * game time (ticks since the game's last reset; the reference's gs.getTime()),
  * env steps of the episode, steps since creation, and three never-reset

@@ -719,6 +719,33 @@ int mrts_sample_actions_src_group(void *stream, const mrts_sample_seg *segs, int
     return mrts_engine_sample_src_group(segs, nseg, seed, step, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
+// the masked action head's shared argument checks: the sampler's row bound (32-bit row indexing)
+static bool policy_shape_ok(int32_t n, int32_t hw) {
+    return n >= 0 && hw >= 1 && (int64_t)n * hw <= (int64_t)INT32_MAX - 256;
+}
+
+int mrts_policy_sample(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw,
+                       int32_t env0, uint64_t seed, uint32_t step, int64_t *actions, float *logprob, float *entropy) {
+    if (!logits || !mask || !source || !actions || !logprob || !entropy || env0 < 0 || !policy_shape_ok(n, hw)) return MRTS_EINVAL;
+    return mrts_engine_policy_sample(logits, mask, source, n, hw, env0, seed, step, actions, logprob, entropy, (hipStream_t)stream)
+               ? MRTS_EHIP : MRTS_OK;
+}
+
+int mrts_policy_evaluate(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw,
+                         const int64_t *actions, float *logprob, float *entropy) {
+    if (!logits || !mask || !source || !actions || !logprob || !entropy || !policy_shape_ok(n, hw)) return MRTS_EINVAL;
+    return mrts_engine_policy_eval(logits, mask, source, n, hw, actions, logprob, entropy, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
+int mrts_policy_evaluate_backward(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n,
+                                  int32_t hw, const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
+                                  float *grad_logits) {
+    if (!logits || !mask || !source || !actions || !grad_logprob || !grad_entropy || !grad_logits || !policy_shape_ok(n, hw))
+        return MRTS_EINVAL;
+    return mrts_engine_policy_eval_bwd(logits, mask, source, n, hw, actions, grad_logprob, grad_entropy, grad_logits,
+                                       (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
 int mrts_bind_mask_outputs(mrts_vec *h, int32_t *mask, int32_t *source) {
     if (!bound(h)) return fail(h, MRTS_ESTATE, "bind_mask_outputs: workspace not bound");
     if ((mask == nullptr) != (source == nullptr)) return fail(h, MRTS_EINVAL, "bind_mask_outputs: mask and source go together");

@@ -100,6 +100,13 @@ hipError_t mrts_engine_sample(const int32_t *mask, int n, int hw, int env0, uint
 hipError_t mrts_engine_sample_src(const int32_t *mask, const int32_t *src, int n, int hw, int env0, uint64_t seed, uint32_t step,
                                   int64_t *act, hipStream_t s);
 hipError_t mrts_engine_sample_src_group(const mrts_sample_seg *segs, int nseg, uint64_t seed, uint32_t step, hipStream_t s);
+// mrts_policy.hip: the masked action head (sample / evaluate / evaluate's backward)
+hipError_t mrts_engine_policy_sample(const float *logits, const int32_t *mask, const int32_t *src, int n, int hw, int env0,
+                                     uint64_t seed, uint32_t step, int64_t *act, float *logprob, float *entropy, hipStream_t s);
+hipError_t mrts_engine_policy_eval(const float *logits, const int32_t *mask, const int32_t *src, int n, int hw, const int64_t *act,
+                                   float *logprob, float *entropy, hipStream_t s);
+hipError_t mrts_engine_policy_eval_bwd(const float *logits, const int32_t *mask, const int32_t *src, int n, int hw, const int64_t *act,
+                                       const float *g_lp, const float *g_ent, float *grad, hipStream_t s);
 hipError_t mrts_engine_render(const EngineParams *p, hipStream_t s, int game, int map, int size, uint8_t *rgb);
 size_t mrts_engine_lds_bytes(int HW, int W);
 size_t mrts_engine_bot_lds_bytes(int HW, int W);

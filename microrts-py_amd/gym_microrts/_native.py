@@ -104,6 +104,10 @@ SIGNATURES = {
     "mrts_sample_actions_src": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
                                                ctypes.c_uint32, P]),
     "mrts_sample_actions_src_group": (ctypes.c_int, [P, P, ctypes.c_int32, ctypes.c_uint64, ctypes.c_uint32]),
+    "mrts_policy_sample": (ctypes.c_int, [P, P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                          ctypes.c_uint32, P, P, P]),
+    "mrts_policy_evaluate": (ctypes.c_int, [P, P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P]),
+    "mrts_policy_evaluate_backward": (ctypes.c_int, [P, P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P, P]),
     "mrts_game_stats": (ctypes.c_int, [P, P, P]),
     "mrts_bind_mask_outputs": (ctypes.c_int, [P, P, P]),
     "mrts_set_bot_fusion": (ctypes.c_int, [P, ctypes.c_int32]),
