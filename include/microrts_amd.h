@@ -212,14 +212,18 @@ int mrts_add_map(mrts_vec *h, void *stream, const char *path, int32_t *index);
 /* Random masked action sampler of hello_world.py:27-64 on the device
  * (Philox4x32-10 keyed by seed, counter = (cell, env0 + env, step)): env0 is the
  * global index of row 0's env, so a shard draws the actions of its slice of
- * one larger batch.  Not a reference entry point: the bench's stand-in policy. */
+ * one larger batch.  Not a reference entry point: the bench's stand-in policy.
+ * MRTS_EINVAL before any launch: a null pointer, hw < 1, num_envs < 0, env0 < 0,
+ * num_envs * hw beyond 2^31 - 256, actions not 16-byte aligned (the rows are
+ * written with 16-byte stores). */
 int mrts_sample_actions(void *stream, const int32_t *mask, int32_t num_envs, int32_t hw, int32_t env0, uint64_t seed,
                         uint32_t step, int64_t *actions);
 
-/* Same stream and output as mrts_sample_actions, given the source channel too
- * (num_envs * hw must stay below 2^31 - 64: MRTS_EINVAL otherwise):
+/* Same stream and output as mrts_sample_actions, given the source channel too:
  * mask rows of cells whose source is 0 are all zero (getMasks), so only the
- * rows of source cells are read.  Every row's 7 components are still written. */
+ * rows of source cells are read.  Every row's 7 components are still written.
+ * The same checks as mrts_sample_actions (num_envs * hw at most 2^31 - 257,
+ * actions 16-byte aligned: MRTS_EINVAL otherwise). */
 int mrts_sample_actions_src(void *stream, const int32_t *mask, const int32_t *source, int32_t num_envs, int32_t hw,
                             int32_t env0, uint64_t seed, uint32_t step, int64_t *actions);
 

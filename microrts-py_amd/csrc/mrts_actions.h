@@ -1,0 +1,69 @@
+// mrts_actions.h -- the action row, stated once for host and device.
+//
+// One row per (env, cell): the reference's action_plane_space.nvec (vec_env.py:234),
+// seven components.  get_action_mask's 78 channels are the components' entries laid
+// end to end (component k owns channels ACT_OFF[k] .. ACT_OFF[k] + ACT_LEN[k] - 1);
+// getMasks' 79-bit word puts the source bit in front (channel ch = bit ch + 1).
+// Users: decode_row (mrts_engine.hip), cell_mask (mrts_rules.h), the stand-in samplers
+// (mrts_sampler.hip), the masked action head (mrts_policy.hip).  The oracle keeps
+// tables of its own: it is the independent reference.
+#ifndef MRTS_ACTIONS_H
+#define MRTS_ACTIONS_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "mrts_layout.h"
+
+namespace mrts {
+
+enum { A_NONE = 0, A_MOVE, A_HARVEST, A_RETURN, A_PRODUCE, A_ATTACK };   // UnitAction.TYPE_*: the action-type component's values
+enum { ACT_TYPE = 0, ACT_MOVE_DIR, ACT_HARVEST_DIR, ACT_RETURN_DIR, ACT_PRODUCE_DIR, ACT_PRODUCE_TYPE, ACT_ATTACK_CELL,
+       ACT_COMPONENTS };
+constexpr int ACT_OFF[ACT_COMPONENTS] = {0, 6, 10, 14, 18, 22, 29};
+constexpr int ACT_LEN[ACT_COMPONENTS] = {6, 4, 4, 4, 4, 7, 49};
+
+constexpr bool act_offsets_are_running_sums() {
+    int sum = 0;
+    for (int k = 0; k < ACT_COMPONENTS; k++) {
+        if (ACT_OFF[k] != sum) return false;
+        sum += ACT_LEN[k];
+    }
+    return sum == MRTS_MASK_CH;
+}
+static_assert(act_offsets_are_running_sums(), "ACT_OFF is the running sum of ACT_LEN, MRTS_MASK_CH their total");
+static_assert(MRTS_MASK_BITS == MRTS_MASK_CH + 1, "the source bit in front of the channels");
+static_assert(ACT_LEN[ACT_TYPE] == A_ATTACK + 1, "one entry per action type");
+static_assert(ACT_LEN[ACT_MOVE_DIR] == 4 && ACT_LEN[ACT_HARVEST_DIR] == 4 && ACT_LEN[ACT_RETURN_DIR] == 4 && ACT_LEN[ACT_PRODUCE_DIR] == 4,
+              "one entry per direction");
+static_assert(ACT_LEN[ACT_PRODUCE_TYPE] == MRTS_NTYPES, "one entry per unit type");
+static_assert(ACT_LEN[ACT_ATTACK_CELL] == MRTS_ATTACK_GRID * MRTS_ATTACK_GRID, "one entry per cell of the attack grid");
+// decode_row reads the direction of action type ty at r[ty]
+static_assert(ACT_MOVE_DIR == A_MOVE && ACT_HARVEST_DIR == A_HARVEST && ACT_RETURN_DIR == A_RETURN, "direction component = action type");
+
+// Component k's offset and length for a k known only at run time, from packed bytes:
+// a shift and a mask instead of a table in memory (k >= ACT_COMPONENTS: 0, 0).
+constexpr uint64_t act_pack(const int (&t)[ACT_COMPONENTS]) {
+    uint64_t w = 0;
+    for (int k = 0; k < ACT_COMPONENTS; k++) w |= (uint64_t)t[k] << (8 * k);
+    return w;
+}
+static_assert(ACT_COMPONENTS <= 8 && MRTS_MASK_CH < 256, "a byte per component in one 64-bit word");
+constexpr uint64_t ACT_OFF_BYTES = act_pack(ACT_OFF), ACT_LEN_BYTES = act_pack(ACT_LEN);
+__host__ __device__ inline int comp_off(int k) { return (int)((ACT_OFF_BYTES >> (8 * k)) & 0xFF); }
+__host__ __device__ inline int comp_len(int k) { return (int)((ACT_LEN_BYTES >> (8 * k)) & 0xFF); }
+// the component that owns channel ch
+__host__ __device__ inline int comp_of(int ch) {
+    int k = 0;
+    for (int j = 1; j < ACT_COMPONENTS; j++) k += ch >= ACT_OFF[j];
+    return k;
+}
+// a component's valid entries as bits 0 .. len - 1, from a row's 78 channels as bits lo (0..63) | hi (64..77)
+__host__ __device__ inline uint64_t comp_bits(uint64_t lo, uint64_t hi, int off, int len) {
+    return ((lo >> off) | (off ? (hi << (64 - off)) : 0ull)) & ((1ull << len) - 1ull);
+}
+// A uniform pick among n entries from one random word.  With n = the component's length it
+// is the no-valid-entry draw: what every sampler writes for a component the mask leaves empty.
+__host__ __device__ inline int draw_uniform(uint32_t r, int n) { return (int)(((uint64_t)r * (uint32_t)n) >> 32); }
+
+}  // namespace mrts
+#endif

@@ -695,16 +695,22 @@ int mrts_park_games(mrts_vec *h, void *stream, const int32_t *games, int32_t cou
     return e ? hip_fail(h, e, "park_games launch") : MRTS_OK;
 }
 
+// The samplers' and the action head's shared shape check: the kernels index the n * hw rows
+// in 32 bits, a wave's 64-row group rounded up.
+static bool sampler_rows_ok(int32_t n, int32_t hw) { return n >= 0 && hw >= 1 && (int64_t)n * hw <= (int64_t)INT32_MAX - 256; }
+// The stand-in samplers write the action rows with 16-byte stores from an address derived
+// from `actions` (the action head's sampler has a per-element path instead).
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
+
 int mrts_sample_actions(void *stream, const int32_t *mask, int32_t n, int32_t hw, int32_t env0, uint64_t seed, uint32_t step,
                         int64_t *actions) {
-    if (!mask || !actions || n < 0 || hw <= 0 || env0 < 0) return MRTS_EINVAL;
+    if (!mask || !actions || env0 < 0 || !sampler_rows_ok(n, hw) || !aligned16(actions)) return MRTS_EINVAL;
     return mrts_engine_sample(mask, n, hw, env0, seed, step, actions, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
 int mrts_sample_actions_src(void *stream, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw, int32_t env0,
                             uint64_t seed, uint32_t step, int64_t *actions) {
-    if (!mask || !source || !actions || n < 0 || hw <= 0 || env0 < 0) return MRTS_EINVAL;
-    if ((int64_t)n * hw > (int64_t)INT32_MAX - 256) return MRTS_EINVAL;   // k_sample_src indexes rows in 32 bits
+    if (!mask || !source || !actions || env0 < 0 || !sampler_rows_ok(n, hw) || !aligned16(actions)) return MRTS_EINVAL;
     return mrts_engine_sample_src(mask, source, n, hw, env0, seed, step, actions, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
@@ -712,35 +718,29 @@ int mrts_sample_actions_src_group(void *stream, const mrts_sample_seg *segs, int
     if (!segs || nseg < 1 || nseg > MRTS_SAMPLE_GROUP_MAX) return MRTS_EINVAL;
     for (int k = 0; k < nseg; k++) {
         const mrts_sample_seg &q = segs[k];
-        if (!q.mask || !q.source || !q.actions || q.num_envs < 0 || q.hw <= 0 || q.env0 < 0) return MRTS_EINVAL;
-        if ((int64_t)q.num_envs * q.hw > (int64_t)INT32_MAX - 256) return MRTS_EINVAL;   // 32-bit row indexing
-        if ((uintptr_t)q.actions & 15u) return MRTS_EINVAL;   // the rows' 16-byte stores
+        if (!q.mask || !q.source || !q.actions || q.env0 < 0 || !sampler_rows_ok(q.num_envs, q.hw) || !aligned16(q.actions))
+            return MRTS_EINVAL;
     }
     return mrts_engine_sample_src_group(segs, nseg, seed, step, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
-// the masked action head's shared argument checks: the sampler's row bound (32-bit row indexing)
-static bool policy_shape_ok(int32_t n, int32_t hw) {
-    return n >= 0 && hw >= 1 && (int64_t)n * hw <= (int64_t)INT32_MAX - 256;
-}
-
 int mrts_policy_sample(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw,
                        int32_t env0, uint64_t seed, uint32_t step, int64_t *actions, float *logprob, float *entropy) {
-    if (!logits || !mask || !source || !actions || !logprob || !entropy || env0 < 0 || !policy_shape_ok(n, hw)) return MRTS_EINVAL;
+    if (!logits || !mask || !source || !actions || !logprob || !entropy || env0 < 0 || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
     return mrts_engine_policy_sample(logits, mask, source, n, hw, env0, seed, step, actions, logprob, entropy, (hipStream_t)stream)
                ? MRTS_EHIP : MRTS_OK;
 }
 
 int mrts_policy_evaluate(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw,
                          const int64_t *actions, float *logprob, float *entropy) {
-    if (!logits || !mask || !source || !actions || !logprob || !entropy || !policy_shape_ok(n, hw)) return MRTS_EINVAL;
+    if (!logits || !mask || !source || !actions || !logprob || !entropy || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
     return mrts_engine_policy_eval(logits, mask, source, n, hw, actions, logprob, entropy, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
 int mrts_policy_evaluate_backward(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n,
                                   int32_t hw, const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
                                   float *grad_logits) {
-    if (!logits || !mask || !source || !actions || !grad_logprob || !grad_entropy || !grad_logits || !policy_shape_ok(n, hw))
+    if (!logits || !mask || !source || !actions || !grad_logprob || !grad_entropy || !grad_logits || !sampler_rows_ok(n, hw))
         return MRTS_EINVAL;
     return mrts_engine_policy_eval_bwd(logits, mask, source, n, hw, actions, grad_logprob, grad_entropy, grad_logits,
                                        (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;

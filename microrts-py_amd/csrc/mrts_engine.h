@@ -1,11 +1,16 @@
 // mrts_engine.h -- internal launch interface between the C ABI (mrts_capi.cpp)
-// and the kernels (mrts_engine.hip).
+// and the kernels: the game step, output streams and renderer (mrts_engine.hip),
+// the scripted opponents (mrts_bots.hip), the stand-in samplers (mrts_sampler.hip)
+// and the masked action head (mrts_policy.hip).
 #ifndef MRTS_ENGINE_H
 #define MRTS_ENGINE_H
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "microrts_amd.h"   // mrts_sample_seg, MRTS_* limits
+
+// four int32 as one 16-byte value: the operand of the kernels' 16-byte and non-temporal loads / stores
+namespace mrts { typedef int v4i __attribute__((ext_vector_type(4))); }
 
 // Phase stamps (tracing, experiment builds only: `make STAMPS=1`): each step
 // workgroup takes a row of g_stamp and writes wall_clock64() (100 MHz) at its
@@ -96,6 +101,7 @@ size_t mrts_engine_group_lds_bytes(int HW, int W, int fused, int NT, int partial
 int mrts_engine_step_nt(int HW, int fused);
 hipError_t mrts_engine_bots(const EngineParams *p, hipStream_t s);
 hipError_t mrts_engine_raw_obs(const EngineParams *p, hipStream_t s, int32_t *raw);
+// mrts_sampler.hip: the stand-in samplers (n * hw within 32 bits, actions 16-byte aligned: mrts_capi.cpp checks)
 hipError_t mrts_engine_sample(const int32_t *mask, int n, int hw, int env0, uint64_t seed, uint32_t step, int64_t *act, hipStream_t s);
 hipError_t mrts_engine_sample_src(const int32_t *mask, const int32_t *src, int n, int hw, int env0, uint64_t seed, uint32_t step,
                                   int64_t *act, hipStream_t s);
@@ -107,6 +113,7 @@ hipError_t mrts_engine_policy_eval(const float *logits, const int32_t *mask, con
                                    float *logprob, float *entropy, hipStream_t s);
 hipError_t mrts_engine_policy_eval_bwd(const float *logits, const int32_t *mask, const int32_t *src, int n, int hw, const int64_t *act,
                                        const float *g_lp, const float *g_ent, float *grad, hipStream_t s);
+// mrts_engine.hip again (mrts_engine_bot_lds_bytes: mrts_bots.hip)
 hipError_t mrts_engine_render(const EngineParams *p, hipStream_t s, int game, int map, int size, uint8_t *rgb);
 size_t mrts_engine_lds_bytes(int HW, int W);
 size_t mrts_engine_bot_lds_bytes(int HW, int W);

@@ -17,18 +17,20 @@
 // per-cell bit words in LDS (one-hot obs: 1 word/cell, mask: 3 words/cell).
 // A step launch takes a StepGroup: one or more engines (map-size buckets) cut
 // into grid segments, bot games first (mrts_step_group).
+// In this unit: the game step, the output streams (reset / masks / outputs / raw obs),
+// the renderer, their launchers.  Elsewhere: the scripted opponents (mrts_bots.hip), the
+// stand-in samplers (mrts_sampler.hip), the masked action head (mrts_policy.hip).
 //
 // Integer work only: no MFMA, the kernels are HBM-bound on the obs/mask writes.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include <algorithm>
-#include <mutex>
-#include <vector>
+#include <type_traits>
 
+#include "mrts_actions.h"
 #include "mrts_engine.h"
 #include "mrts_layout.h"
-#include "mrts_philox.h"
 
 #include "mrts_rules.h"
 #include "mrts_bots.h"
@@ -70,8 +72,6 @@ enum { SC_TIME = MRTS_G_TIME, SC_RES0 = MRTS_G_RES0, SC_RES1 = MRTS_G_RES1, SC_U
        SC_NREADY = 38 /* ready assignments listed in L.list */, SC_NLEFT = 39 /* rows (2a) left to the ordered path */,
        SC_WORDS = 40 };
 static_assert(MRTS_GENV_WORDS <= SC_R0, "genv words overlap the LDS scalars");
-
-typedef int v4i __attribute__((ext_vector_type(4)));
 
 // 16-byte store of an output row segment (obs / masks: written once, read by
 // the consumer after the kernel; plain stores measured 5 % faster than
@@ -1137,20 +1137,20 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     // legality + the target claims; returns its aux word
     auto decode_row = [&](int c, int v, int ow) -> uint32_t {
         const int64_t* ra = p.actions + ((size_t)(G.env0 + v) * HW + c) * 7;
-        int64_t r[7];   // all 7 components in one round trip
+        int64_t r[ACT_COMPONENTS];   // all 7 components in one round trip
 #pragma unroll
-        for (int k = 0; k < 7; k++) r[k] = ra[k];
-        int64_t ty = r[0];
+        for (int k = 0; k < ACT_COMPONENTS; k++) r[k] = ra[k];
+        int64_t ty = r[ACT_TYPE];
         int code = -1;
         if (ty == A_NONE) code = code_make(A_NONE, 1, 0);   // NONE(1): param = duration
         else if (ty >= A_MOVE && ty <= A_RETURN) {
-            int64_t d = r[ty];
+            int64_t d = r[ty];   // the direction component of type ty is component ty (mrts_actions.h)
             if (d >= 0 && d < 4) code = code_make((int)ty, (int)d, 0);
         } else if (ty == A_PRODUCE) {
-            int64_t d = r[4], t2 = r[5];
+            int64_t d = r[ACT_PRODUCE_DIR], t2 = r[ACT_PRODUCE_TYPE];
             if (d >= 0 && d < 4 && t2 >= 0 && t2 < MRTS_NTYPES) code = code_make(A_PRODUCE, (int)d, (int)t2);
         } else if (ty == A_ATTACK) {
-            int64_t a = r[6];
+            int64_t a = r[ACT_ATTACK_CELL];
             if (a >= 0 && a < MRTS_ATTACK_GRID * MRTS_ATTACK_GRID) code = code_make(A_ATTACK, (int)a, 0);
         }
         if (code < 0) return 0u;
@@ -1530,252 +1530,27 @@ __global__ __launch_bounds__(256) void k_render(const int4* __restrict__ cells, 
 }
 
 // ---------------------------------------------------------------------------
-// Counter-based masked sampler (hello_world.py:27-64 semantics), Philox4x32-10
-// keyed (seed) with counter (cell, env, step, half) -- identical stream to the
-// oracle's ovec_sample_actions.  `env` is the GLOBAL env index (env0 + local
-// row), so a shard of envs [env0, env0 + n) draws exactly the actions of that
-// slice of one larger run (multi-GPU sharding).
-// philox / philox_row (the row's eight random words): mrts_philox.h, shared with
-// the masked action head (mrts_policy.hip).
-//
-// One row (env e, cell c): the 78 mask channels as bits lo (0..63) | hi (64..77);
-// per component k, a uniform pick among the valid entries (uniform over all
-// entries when none is valid), from two Philox4x32-10 blocks of counter
-// (c, e, step, 0|1) -- the oracle's ovec_sample_actions stream.
-__device__ __forceinline__ void select_row(uint64_t lo, uint64_t hi, const uint32_t r[8], int64_t* out) {
-    const int off[7] = {0, 6, 10, 14, 18, 22, 29};
-    const int len[7] = {6, 4, 4, 4, 4, 7, 49};
-#pragma unroll
-    for (int k = 0; k < 7; k++) {
-        uint64_t seg = (lo >> off[k]) | (off[k] ? (hi << (64 - off[k])) : 0);   // bits [off, off+len)
-        seg &= (1ull << len[k]) - 1ull;
-        const int nvalid = __popcll(seg);
-        int pick;
-        if (nvalid == 0) {
-            pick = (int)(((uint64_t)r[k] * (uint32_t)len[k]) >> 32);
-        } else {
-            int t = (int)(((uint64_t)r[k] * (uint32_t)nvalid) >> 32);
-            for (; t > 0; t--) seg &= seg - 1ull;   // drop the t lowest set bits
-            pick = __builtin_ctzll(seg);
-        }
-        out[k] = pick;
-    }
-}
-__device__ __forceinline__ void sample_row(uint64_t lo, uint64_t hi, int e, int c, uint64_t seed, uint32_t step, int64_t* out) {
-    uint32_t r[8];
-    philox_row(e, c, seed, step, r);
-    select_row(lo, hi, r, out);
-}
-
-// Persistent, software-pipelined: every WAVE owns groups of SW = 32 consecutive
-// (env, cell) rows (32 x 312 B of int32 mask, contiguous).  While a group is
-// folded into 78-bit words in the wave's LDS slice and sampled (one lane per
-// row), the NEXT group's 10 dwordx4 loads per lane are already in flight in a
-// second register buffer, so the HBM stream never idles behind the Philox /
-// selection arithmetic.  The 7 int64 components per row are staged in LDS and
-// written back with coalesced 16-byte stores.  No block barriers: a wave's own
-// LDS operations complete in order.
-constexpr int SW = 32;                                   // rows per group (one wave)
-constexpr int SWAVES = 4;                                // waves per workgroup
-constexpr int SNV = (SW * MRTS_MASK_CH / 4 + 63) / 64;   // dwordx4 loads per lane per group (10)
-
-
-struct SampleBuf {
-    int4 v[SNV];
-};
-
-__device__ __forceinline__ void sample_load(SampleBuf& B, const int32_t* __restrict__ mask, long long grp, long long rows) {
-    const long long row0 = grp * SW;
-    const int rb = (int)min((long long)SW, rows - row0);
-    const int nv = rb * MRTS_MASK_CH / 4;
-    const int4* m4 = reinterpret_cast<const int4*>(mask + row0 * MRTS_MASK_CH);
-    // Unconditional loads (tail lanes re-read the group's last int4 and are
-    // masked when consumed): no branch around a load, so hipcc can count them and
-    // wait with vmcnt(SNV) for this group while the next one stays in flight.
-#pragma unroll
-    for (int j = 0; j < SNV; j++) {
-        const int k = min(j * 64 + (int)(threadIdx.x & 63), nv - 1);
-        const v4i t = __builtin_nontemporal_load(reinterpret_cast<const v4i*>(m4 + k));   // streamed once
-        B.v[j] = make_int4(t.x, t.y, t.z, t.w);
-    }
-}
-
-__device__ __forceinline__ void sample_group(const SampleBuf& B, const int32_t* __restrict__ mask, long long grp, long long rows,
-                                             int hw, int env0, uint64_t seed, uint32_t step, int64_t* __restrict__ act,
-                                             uint32_t* s_bits, int64_t* s_out) {
-    const int lane = threadIdx.x & 63;
-    const long long row0 = grp * SW;
-    const int rb = (int)min((long long)SW, rows - row0);
-    const int nel = rb * MRTS_MASK_CH, nv = nel >> 2;
-    for (int i = lane; i < SW * 3; i += 64) s_bits[i] = 0;
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-#pragma unroll
-    for (int j = 0; j < SNV; j++) {
-        const int k = j * 64 + lane;
-        const int4 v = B.v[j];
-        if (k >= nv || (v.x | v.y | v.z | v.w) == 0) continue;   // most cells hold no idle unit
-        int e = 4 * k;
-        int r = e / MRTS_MASK_CH, ch = e - r * MRTS_MASK_CH;
-        const int vv[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            if (vv[q]) atomicOr(&s_bits[3 * r + (ch >> 5)], 1u << (ch & 31));
-            if (++ch == MRTS_MASK_CH) { ch = 0; r++; }
-        }
-    }
-    for (int e = 4 * nv + lane; e < nel; e += 64) {   // odd row count: the last 2 int32
-        if (mask[row0 * MRTS_MASK_CH + e]) {
-            int r = e / MRTS_MASK_CH, ch = e - r * MRTS_MASK_CH;
-            atomicOr(&s_bits[3 * r + (ch >> 5)], 1u << (ch & 31));
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    if (lane < rb) {
-        const long long idx = row0 + lane;
-        const int e = (int)(idx / hw), c = (int)(idx - (long long)e * hw);
-        const uint64_t lo = (uint64_t)s_bits[3 * lane] | ((uint64_t)s_bits[3 * lane + 1] << 32);
-        const uint64_t hi = s_bits[3 * lane + 2];
-        sample_row(lo, hi, env0 + e, c, seed, step, s_out + lane * 7);
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    int64_t* ob = act + row0 * 7;   // 16-B aligned: SW * 56 B per group
-    const int onel = rb * 7, onv = onel >> 1;
-    int4* o4 = reinterpret_cast<int4*>(ob);
-    const int4* s4 = reinterpret_cast<const int4*>(s_out);
-    for (int k = lane; k < onv; k += 64) o4[k] = s4[k];
-    if ((onel & 1) && lane == 0) ob[onel - 1] = s_out[onel - 1];
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-}
-
-constexpr int SAMPLE_BLOCKS_PER_CU = 16;   // measured best (round 1: 2 -> 151 us, 4 -> 138, 8 -> 133, 16 -> 127, 64 -> 178)
-__global__ __launch_bounds__(64 * SWAVES) void k_sample(const int32_t* __restrict__ mask, int n, int hw, int env0,
-                                                        uint64_t seed, uint32_t step, int64_t* __restrict__ act) {
-    __shared__ uint32_t s_bits[SWAVES][SW * 3];
-    __shared__ __attribute__((aligned(16))) int64_t s_out[SWAVES][SW * 7];
-    const int w = threadIdx.x >> 6;
-    const long long rows = (long long)n * hw;
-    const long long ngrp = (rows + SW - 1) / SW;
-    const long long stride = (long long)gridDim.x * SWAVES;
-    long long grp = (long long)blockIdx.x * SWAVES + w;
-    if (grp >= ngrp) return;
-    SampleBuf A, B;
-    sample_load(A, mask, grp, rows);
-    while (true) {   // two groups per trip: A is consumed while B loads, then the reverse
-        const long long g1 = grp + stride;   // past the end: a harmless re-read of the last group
-        sample_load(B, mask, min(g1, ngrp - 1), rows);
-        sample_group(A, mask, grp, rows, hw, env0, seed, step, act, s_bits[w], s_out[w]);
-        if (g1 >= ngrp) break;
-        const long long g2 = g1 + stride;
-        sample_load(A, mask, min(g2, ngrp - 1), rows);
-        sample_group(B, mask, g1, rows, hw, env0, seed, step, act, s_bits[w], s_out[w]);
-        if (g2 >= ngrp) break;
-        grp = g2;
-    }
-}
-
-// Source-guided variant: the same stream and output, given the source channel
-// as well.  getMasks sets no channel of a cell whose source bit is 0 (no idle
-// unit of the player: UnitAction.getValidActionArray is all zero), so only the
-// mask rows of source cells are read -- a few per cent of the 78-channel rows
-// on basesWorkers -- while every row's 7 components are still drawn and
-// written.  One wave per 64 consecutive rows: the wave reads the rows of its
-// active lanes cooperatively (channel k on lane k, two coalesced loads per row,
-// up to SRC_ROWS (4) rows in flight) and folds each with two ballots.  Measured
-// and refuted in round 5 (profiles/r05_ab/): writing every row's no-valid-entry
-// draw first and patching the source rows after (sampler 32.6 -> 35.6 us, and the
-// next k_step +8 us); two 64-row groups per wave sharing one chain of round trips
-// (32.7 -> 32.4 us, configs[1] 2 % slower).
-constexpr int SR_WAVES = 4;
-constexpr int SRC_ROWS = 4;   // source rows per round trip (8 and 16 measured slower, profiles/r04_ab/r04v)
-// one block's 4 x 64 rows of one batch (k_sample_src: block = blockIdx.x; the grouped
-// launch: the block's index inside its segment)
-__device__ __forceinline__ void sample_src_block(const int32_t* __restrict__ mask, const int32_t* __restrict__ src, int n, int hw,
-                                                 int env0, uint64_t seed, uint32_t step, int64_t* __restrict__ act, long long blk,
-                                                 int64_t (*s_out)[64 * 7]) {
-    const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    const long long rows = (long long)n * hw;
-    const long long row0 = (blk * SR_WAVES + w) * 64;
-    if (row0 >= rows) return;
-    const int rb = (int)min(64ll, rows - row0);
-    const bool in = lane < rb;
-    // unconditional load (tail lanes re-read the last row): no branch around it, so
-    // its wait falls after the row's Philox words, which are drawn while the source
-    // word (and then the mask rows) are in flight
-    const int s_raw = src[row0 + min(lane, rb - 1)];
-    uint32_t r8[8];
-    const unsigned idx = (unsigned)(row0 + lane);   // rows = n * hw < 2^31 (mrts_sample_actions_src checks)
-    const int e = (int)(idx / (unsigned)hw), c = (int)(idx - (unsigned)e * (unsigned)hw);
-    philox_row(env0 + e, c, seed, step, r8);
-#pragma unroll
-    for (int k = 0; k < 8; k++) asm volatile("" : "+v"(r8[k]));   // computed here, not sunk to their use after the loads
-    const int s = in ? s_raw : 0;
-    uint64_t pending = __ballot(s != 0);
-    uint64_t lo = 0, hi = 0;   // this lane's row as 78 bits
-    while (pending) {          // wave-uniform; SRC_ROWS source rows per round trip
-        int r[SRC_ROWS];
-#pragma unroll
-        for (int k = 0; k < SRC_ROWS; k++) {
-            r[k] = pending ? __builtin_ctzll(pending) : r[0];   // repeats r[0]
-            pending &= pending - 1ull;
-        }
-        int v0[SRC_ROWS], v1[SRC_ROWS];
-#pragma unroll
-        for (int k = 0; k < SRC_ROWS; k++) {   // all the loads in flight before the first ballot
-            const int32_t* m = mask + (row0 + r[k]) * MRTS_MASK_CH;   // (a repeated row re-reads the same bits)
-            v0[k] = __builtin_nontemporal_load(m + lane);
-            v1[k] = __builtin_nontemporal_load(m + 64 + min(lane, MRTS_MASK_CH - 65));
-        }
-#pragma unroll
-        for (int k = 0; k < SRC_ROWS; k++) {
-            const uint64_t b0 = __ballot(v0[k] != 0);
-            const uint64_t b1 = __ballot(lane < MRTS_MASK_CH - 64 && v1[k] != 0);
-            if (lane == r[k]) { lo = b0; hi = b1; }
-        }
-    }
-    if (in) select_row(lo, hi, r8, s_out[w] + lane * 7);
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    int64_t* ob = act + row0 * 7;   // 16-B aligned: 64 * 56 B per wave
-    const int onel = rb * 7, onv = onel >> 1;
-    int4* o4 = reinterpret_cast<int4*>(ob);
-    const int4* s4 = reinterpret_cast<const int4*>(s_out[w]);
-    for (int k = lane; k < onv; k += 64) {   // non-temporal: k_step reads ~2 % of the rows back
-        const int4 t = s4[k];
-        const v4i v = {t.x, t.y, t.z, t.w};
-        __builtin_nontemporal_store(v, reinterpret_cast<v4i*>(o4 + k));
-    }
-    if ((onel & 1) && lane == 0) ob[onel - 1] = s_out[w][onel - 1];
-}
-__global__ __launch_bounds__(64 * SR_WAVES) void k_sample_src(const int32_t* __restrict__ mask, const int32_t* __restrict__ src, int n,
-                                                           int hw, int env0, uint64_t seed, uint32_t step,
-                                                           int64_t* __restrict__ act) {
-    __shared__ __attribute__((aligned(16))) int64_t s_out[SR_WAVES][64 * 7];
-    sample_src_block(mask, src, n, hw, env0, seed, step, act, blockIdx.x, s_out);
-}
-// Several batches (a mixed batch's size buckets) in one launch: segment k owns blocks
-// [end[k-1], end[k]); a block finds its segment with a scalar scan of the table.
-struct SampleSeg {
-    const int32_t* mask;
-    const int32_t* src;
-    int64_t* act;
-    int n, hw, env0;
-};
-struct SampleGroup {
-    SampleSeg seg[MRTS_SAMPLE_GROUP_MAX];
-    long long end[MRTS_SAMPLE_GROUP_MAX];
-    int nseg;
-};
-__global__ __launch_bounds__(64 * SR_WAVES) void k_sample_src_group(const SampleGroup g, uint64_t seed, uint32_t step) {
-    __shared__ __attribute__((aligned(16))) int64_t s_out[SR_WAVES][64 * 7];
-    const long long b = blockIdx.x;
-    int k = 0;
-    while (k + 1 < g.nseg && b >= g.end[k]) k++;
-    const SampleSeg& sg = g.seg[k];
-    sample_src_block(sg.mask, sg.src, sg.n, sg.hw, sg.env0, seed, step, sg.act, b - (k ? g.end[k - 1] : 0), s_out);
-}
-
-// ---------------------------------------------------------------------------
 // launchers
 
+enum Kind { K_RESET, K_MASKS, K_STEP, K_OUTPUTS };
+
+// Workgroup size of a map size: one lane per cell up to 256 lanes; the bot-fused
+// step needs a wave besides the bot's, so maps of <= 64 cells take 128 lanes there.
+__host__ __device__ inline int step_nt(int HW, bool fused) { return HW <= 64 && !fused ? 64 : HW <= 128 ? 128 : 256; }
+
+// f(NT) with a step_nt value, f(planes, obs element) with an engine's obs planes and a value
+// of its obs element type (the kernels' P and OT), as compile-time constants
+template <int N>
+using ic = std::integral_constant<int, N>;
+template <typename F>
+static auto with_nt(int NT, F&& f) {
+    return NT == 64 ? f(ic<64>{}) : NT == 128 ? f(ic<128>{}) : f(ic<256>{});
+}
+template <typename F>
+static void with_obs(bool partial, bool fl, F&& f) {
+    if (partial) fl ? f(ic<31>{}, float{}) : f(ic<31>{}, int32_t{});
+    else fl ? f(ic<29>{}, float{}) : f(ic<29>{}, int32_t{});
+}
 
 // One engine's step launch.  With both selfplay and bot games, the bot games take
 // the first workgroups: workgroups start in grid order, and a bot game's chain (the
@@ -1798,70 +1573,43 @@ static StepGroup one_engine(const EngineParams& p) {
     return sg;
 }
 
-// the step kernel of a launch's (planes, obs type, bot fusion)
+// The step kernel of a launch's (planes, obs type, bot fusion).  No 64-lane launch
+// is fused (step_nt: the fused step needs a wave besides the bot's), so no fused
+// 64-lane kernel is built.
 template <int NT>
 static void launch_step(const StepGroup& sg, int grid, size_t sh, hipStream_t s, bool partial, bool fl, bool fb) {
-    if (fb) {
-        if (partial) {
-            if (fl) hipLaunchKernelGGL((k_step<NT, 31, float, true>), dim3(grid), dim3(NT), sh, s, sg);
-            else hipLaunchKernelGGL((k_step<NT, 31, int32_t, true>), dim3(grid), dim3(NT), sh, s, sg);
-        } else {
-            if (fl) hipLaunchKernelGGL((k_step<NT, 29, float, true>), dim3(grid), dim3(NT), sh, s, sg);
-            else hipLaunchKernelGGL((k_step<NT, 29, int32_t, true>), dim3(grid), dim3(NT), sh, s, sg);
-        }
-    } else {
-        if (partial) {
-            if (fl) hipLaunchKernelGGL((k_step<NT, 31, float>), dim3(grid), dim3(NT), sh, s, sg);
-            else hipLaunchKernelGGL((k_step<NT, 31, int32_t>), dim3(grid), dim3(NT), sh, s, sg);
-        } else {
-            if (fl) hipLaunchKernelGGL((k_step<NT, 29, float>), dim3(grid), dim3(NT), sh, s, sg);
-            else hipLaunchKernelGGL((k_step<NT, 29, int32_t>), dim3(grid), dim3(NT), sh, s, sg);
-        }
-    }
+    with_obs(partial, fl, [&](auto planes, auto ot) {
+        constexpr int P = decltype(planes)::value;
+        using OT = decltype(ot);
+        if (!fb) hipLaunchKernelGGL((k_step<NT, P, OT>), dim3(grid), dim3(NT), sh, s, sg);
+        else if constexpr (NT > 64) hipLaunchKernelGGL((k_step<NT, P, OT, true>), dim3(grid), dim3(NT), sh, s, sg);
+    });
 }
 
-template <int NT>
-static hipError_t launch_all(const EngineParams& p, int kind, hipStream_t s, const int32_t* games, const int32_t* maps, int count) {
-    size_t sh = lds_bytes(p.HW, p.W, NT);
-    int grid = p.G;
-    if (kind == 0) {   // reset
-        grid = games ? count : p.G;
-        if (grid == 0) return hipSuccess;
-        if (p.partial_obs) {
-            if (p.obs_float) hipLaunchKernelGGL((k_reset<NT, 31, float>), dim3(grid), dim3(NT), sh, s, p, games, maps, count);
-            else hipLaunchKernelGGL((k_reset<NT, 31, int32_t>), dim3(grid), dim3(NT), sh, s, p, games, maps, count);
+static hipError_t dispatch(const EngineParams& p, Kind kind, hipStream_t s, const int32_t* games, const int32_t* maps, int count) {
+    return with_nt(step_nt(p.HW, kind == K_STEP && p.fuse_bots), [&](auto nt) -> hipError_t {
+        constexpr int NT = decltype(nt)::value;
+        size_t sh = lds_bytes(p.HW, p.W, NT);
+        int grid = p.G;
+        if (kind == K_RESET) {
+            grid = games ? count : p.G;
+            if (grid == 0) return hipSuccess;
+            with_obs(p.partial_obs, p.obs_float, [&](auto planes, auto ot) {
+                hipLaunchKernelGGL((k_reset<NT, decltype(planes)::value, decltype(ot)>), dim3(grid), dim3(NT), sh, s, p, games, maps, count);
+            });
+        } else if (kind == K_MASKS) {
+            hipLaunchKernelGGL((k_masks<NT>), dim3(grid), dim3(NT), sh, s, p);
+        } else if (kind == K_OUTPUTS) {
+            with_obs(p.partial_obs, p.obs_float, [&](auto planes, auto ot) {
+                hipLaunchKernelGGL((k_outputs<NT, decltype(planes)::value, decltype(ot)>), dim3(grid), dim3(NT), sh, s, p);
+            });
         } else {
-            if (p.obs_float) hipLaunchKernelGGL((k_reset<NT, 29, float>), dim3(grid), dim3(NT), sh, s, p, games, maps, count);
-            else hipLaunchKernelGGL((k_reset<NT, 29, int32_t>), dim3(grid), dim3(NT), sh, s, p, games, maps, count);
+            const bool fb = p.fuse_bots && NT > 64;
+            if (fb) sh = fb_lds_bytes(p.HW, p.W, NT, !p.partial_obs && p.early_bot);
+            launch_step<NT>(one_engine(p), grid, sh, s, p.partial_obs, p.obs_float, fb);
         }
-    } else if (kind == 1) {
-        hipLaunchKernelGGL((k_masks<NT>), dim3(grid), dim3(NT), sh, s, p);
-    } else if (kind == 3) {
-        if (p.partial_obs) {
-            if (p.obs_float) hipLaunchKernelGGL((k_outputs<NT, 31, float>), dim3(grid), dim3(NT), sh, s, p);
-            else hipLaunchKernelGGL((k_outputs<NT, 31, int32_t>), dim3(grid), dim3(NT), sh, s, p);
-        } else {
-            if (p.obs_float) hipLaunchKernelGGL((k_outputs<NT, 29, float>), dim3(grid), dim3(NT), sh, s, p);
-            else hipLaunchKernelGGL((k_outputs<NT, 29, int32_t>), dim3(grid), dim3(NT), sh, s, p);
-        }
-    } else {
-        const bool fb = p.fuse_bots && NT > 64;
-        if (fb) sh = fb_lds_bytes(p.HW, p.W, NT, !p.partial_obs && p.early_bot);
-        launch_step<NT>(one_engine(p), grid, sh, s, p.partial_obs, p.obs_float, fb);
-    }
-    return hipGetLastError();
-}
-
-// Workgroup size of a map size: one lane per cell up to 256 lanes; the bot-fused
-// step needs a wave besides the bot's, so maps of <= 64 cells take 128 lanes there.
-__host__ __device__ inline int step_nt(int HW, bool fused) { return HW <= 64 && !fused ? 64 : HW <= 128 ? 128 : 256; }
-
-static hipError_t dispatch(const EngineParams& p, int kind, hipStream_t s, const int32_t* games, const int32_t* maps, int count) {
-    if (kind == 2 && p.fuse_bots) return step_nt(p.HW, true) == 128 ? launch_all<128>(p, kind, s, games, maps, count)
-                                                                      : launch_all<256>(p, kind, s, games, maps, count);
-    if (p.HW <= 64) return launch_all<64>(p, kind, s, games, maps, count);
-    if (p.HW <= 128) return launch_all<128>(p, kind, s, games, maps, count);
-    return launch_all<256>(p, kind, s, games, maps, count);
+        return hipGetLastError();
+    });
 }
 
 // One step launch over n engines of equal planes, obs type and bot fusion, at the
@@ -1907,9 +1655,7 @@ static hipError_t step_group(const EngineParams* ps, int n, hipStream_t s, bool 
         }
     sg.seg_block[sg.nseg] = grid;
     if (grid == 0) return hipSuccess;
-    if (NT == 64) launch_step<64>(sg, grid, sh, s, p0.partial_obs, p0.obs_float, false);
-    else if (NT == 128) launch_step<128>(sg, grid, sh, s, p0.partial_obs, p0.obs_float, fused);
-    else launch_step<256>(sg, grid, sh, s, p0.partial_obs, p0.obs_float, fused);
+    with_nt(NT, [&](auto nt) { launch_step<decltype(nt)::value>(sg, grid, sh, s, p0.partial_obs, p0.obs_float, fused); });
     return hipGetLastError();
 }
 
@@ -1934,19 +1680,18 @@ int mrts_debug_stamps(unsigned long long* out, int max_rows, int reset) {
 }
 #endif
 hipError_t mrts_engine_reset(const EngineParams* p, hipStream_t s, const int32_t* games, const int32_t* maps, int count) {
-    return mrts::dispatch(*p, 0, s, games, maps, count);
+    return mrts::dispatch(*p, mrts::K_RESET, s, games, maps, count);
 }
-hipError_t mrts_engine_masks(const EngineParams* p, hipStream_t s) { return mrts::dispatch(*p, 1, s, nullptr, nullptr, 0); }
-hipError_t mrts_engine_outputs(const EngineParams* p, hipStream_t s) { return mrts::dispatch(*p, 3, s, nullptr, nullptr, 0); }
+hipError_t mrts_engine_masks(const EngineParams* p, hipStream_t s) { return mrts::dispatch(*p, mrts::K_MASKS, s, nullptr, nullptr, 0); }
+hipError_t mrts_engine_outputs(const EngineParams* p, hipStream_t s) { return mrts::dispatch(*p, mrts::K_OUTPUTS, s, nullptr, nullptr, 0); }
 hipError_t mrts_engine_raw_obs(const EngineParams* p, hipStream_t s, int32_t* raw) {
-    const int NT = p->HW <= 64 ? 64 : p->HW <= 128 ? 128 : 256;
     const size_t sh = mrts_engine_lds_bytes(p->HW, p->W);
-    if (NT == 64) hipLaunchKernelGGL(mrts::k_raw<64>, dim3(p->G), dim3(64), sh, s, *p, raw);
-    else if (NT == 128) hipLaunchKernelGGL(mrts::k_raw<128>, dim3(p->G), dim3(128), sh, s, *p, raw);
-    else hipLaunchKernelGGL(mrts::k_raw<256>, dim3(p->G), dim3(256), sh, s, *p, raw);
+    mrts::with_nt(mrts::step_nt(p->HW, false), [&](auto nt) {
+        hipLaunchKernelGGL(mrts::k_raw<decltype(nt)::value>, dim3(p->G), dim3(decltype(nt)::value), sh, s, *p, raw);
+    });
     return hipGetLastError();
 }
-hipError_t mrts_engine_step(const EngineParams* p, hipStream_t s) { return mrts::dispatch(*p, 2, s, nullptr, nullptr, 0); }
+hipError_t mrts_engine_step(const EngineParams* p, hipStream_t s) { return mrts::dispatch(*p, mrts::K_STEP, s, nullptr, nullptr, 0); }
 hipError_t mrts_engine_step_group(const EngineParams* ps, int n, hipStream_t s, int bots_first) {
     return mrts::step_group(ps, n, s, bots_first != 0);
 }
@@ -1954,37 +1699,6 @@ size_t mrts_engine_group_lds_bytes(int HW, int W, int fused, int NT, int partial
     return fused ? mrts::fb_lds_bytes(HW, W, NT, !partial && mrts::early_bot_disjoint(HW, W, NT)) : mrts::lds_bytes(HW, W, NT);
 }
 int mrts_engine_step_nt(int HW, int fused) { return mrts::step_nt(HW, fused != 0); }
-hipError_t mrts_engine_sample(const int32_t* mask, int n, int hw, int env0, uint64_t seed, uint32_t step, int64_t* act, hipStream_t s) {
-    int total = n * hw;
-    if (total == 0) return hipSuccess;
-    // persistent grid: enough waves to keep every CU streaming, each looping over row groups
-    const long long groups = ((long long)total + mrts::SW - 1) / mrts::SW;
-    const long long blocks = std::min<long long>((groups + mrts::SWAVES - 1) / mrts::SWAVES, 256 * mrts::SAMPLE_BLOCKS_PER_CU);   // resident blocks
-    hipLaunchKernelGGL(mrts::k_sample, dim3((unsigned)blocks), dim3(64 * mrts::SWAVES), 0, s, mask, n, hw, env0, seed, step, act);
-    return hipGetLastError();
-}
-hipError_t mrts_engine_sample_src(const int32_t* mask, const int32_t* src, int n, int hw, int env0, uint64_t seed, uint32_t step,
-                                  int64_t* act, hipStream_t s) {
-    const long long rows = (long long)n * hw;
-    if (rows == 0) return hipSuccess;
-    const long long blocks = (rows + 64 * mrts::SR_WAVES - 1) / (64 * mrts::SR_WAVES);
-    hipLaunchKernelGGL(mrts::k_sample_src, dim3((unsigned)blocks), dim3(64 * mrts::SR_WAVES), 0, s, mask, src, n, hw, env0, seed, step, act);
-    return hipGetLastError();
-}
-hipError_t mrts_engine_sample_src_group(const mrts_sample_seg* segs, int nseg, uint64_t seed, uint32_t step, hipStream_t s) {
-    mrts::SampleGroup g{};
-    long long blocks = 0;
-    for (int k = 0; k < nseg; k++) {
-        const mrts_sample_seg& q = segs[k];
-        g.seg[k] = mrts::SampleSeg{q.mask, q.source, q.actions, q.num_envs, q.hw, q.env0};
-        blocks += ((long long)q.num_envs * q.hw + 64 * mrts::SR_WAVES - 1) / (64 * mrts::SR_WAVES);
-        g.end[k] = blocks;
-    }
-    g.nseg = nseg;
-    if (blocks == 0) return hipSuccess;
-    hipLaunchKernelGGL(mrts::k_sample_src_group, dim3((unsigned)blocks), dim3(64 * mrts::SR_WAVES), 0, s, g, seed, step);
-    return hipGetLastError();
-}
 hipError_t mrts_engine_render(const EngineParams* p, hipStream_t s, int game, int map, int size, uint8_t* rgb) {
     const int nblk = (size * size + 255) / 256;
     hipLaunchKernelGGL(mrts::k_render, dim3(nblk), dim3(256), 0, s, p->cells + (size_t)game * p->cstride, p->map_wall + (size_t)map * p->HW,
@@ -1997,7 +1711,6 @@ size_t mrts_engine_fused_lds_bytes(int HW, int W, int partial) {
     return mrts::fb_lds_bytes(HW, W, NT, !partial && mrts::early_bot_disjoint(HW, W, NT));
 }
 size_t mrts_engine_lds_bytes(int HW, int W) {
-    int NT = HW <= 64 ? 64 : HW <= 128 ? 128 : 256;
-    return mrts::lds_bytes(HW, W, NT);
+    return mrts::lds_bytes(HW, W, mrts::step_nt(HW, false));
 }
 }

@@ -1,5 +1,5 @@
 // mrts_philox.h -- the Philox4x32-10 stream of the device samplers, one definition
-// for the stand-in sampler (mrts_engine.hip) and the masked action head
+// for the stand-in samplers (mrts_sampler.hip) and the masked action head
 // (mrts_policy.hip): keyed by the seed, counter (cell, env, step, half) -- the
 // oracle's ovec_sample_actions stream.  `env` is the GLOBAL env index (env0 + local
 // row), so a shard of envs [env0, env0 + n) draws exactly the words of that slice of

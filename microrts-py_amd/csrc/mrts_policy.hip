@@ -2,11 +2,11 @@
 // CategoricalMasked per action component (experiments/ppo_gridnet.py:164-167, 215-247)
 // as three launches -- sample, evaluate, and evaluate's backward to the logits.
 //
-// Per row (env e, cell c) and component k (offsets 0, 6, 10, 14, 18, 22, 29; lengths
-// 6, 4, 4, 4, 4, 7, 49), with V = the entries the mask allows (none when source == 0):
+// Per row (env e, cell c) and component k (offsets and lengths: mrts_actions.h), with
+// V = the entries the mask allows (none when source == 0):
 //   V empty : log-prob 0, entropy 0, gradient 0 (the reference's float32 result:
 //             -1e8 + log L rounds to -1e8, the normalised logits are 0); the sampled
-//             action is the stand-in sampler's no-valid-entry draw (r[k] * len) >> 32.
+//             action is the stand-in sampler's no-valid-entry draw (draw_uniform, mrts_actions.h).
 //   else    : M = max_V l, E_j = expf(l_j - M), S = sum_V E_j (float32, ascending j),
 //             log p_a = (l_a - M) - logf(S) for a in V, exactly -1e8f for any other a
 //             (out-of-range ones included: they are compared, never used as an index);
@@ -35,6 +35,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mrts_actions.h"
 #include "mrts_engine.h"
 #include "mrts_layout.h"
 #include "mrts_philox.h"
@@ -45,7 +46,8 @@ namespace policy {
 constexpr int PW = 4;          // waves per workgroup
 constexpr int PT = 64 * PW;
 constexpr float LP_INVALID = -1.0e8f;
-static_assert(MRTS_MASK_CH == 78, "mask row layout");
+static_assert(MRTS_MASK_CH > 64 && MRTS_MASK_CH <= 80, "a row is channels lane and 64 + lane of one wave; WaveRow holds 80");
+static_assert(ACT_OFF[ACT_ATTACK_CELL] <= 64 && ACT_COMPONENTS <= 8, "channels 64.. are the last component's; 8 per-component slots");
 
 enum Mode { SAMPLE, EVAL, BWD };
 
@@ -56,11 +58,6 @@ struct WaveRow {
     int a[8];                          // BWD: the component's action if it is a valid entry, -1 otherwise
     uint32_t rk[8];                    // SAMPLE: the row's Philox words
 };
-
-// component k's offset and length from packed bytes (k >= 7: 0, 0)
-__device__ __forceinline__ int comp_off(int k) { return (int)((0x001D16120E0A0600ull >> (8 * k)) & 0xFF); }
-__device__ __forceinline__ int comp_len(int k) { return (int)((0x0031070404040406ull >> (8 * k)) & 0xFF); }
-__device__ __forceinline__ int comp_of(int ch) { return (ch >= 6) + (ch >= 10) + (ch >= 14) + (ch >= 18) + (ch >= 22) + (ch >= 29); }
 
 // a source row's words as loaded: channels lane and 64 + lane (lanes >= 14 re-read channel
 // 77 and ignore it), and lane k < 7's action of component k (EVAL / BWD)
@@ -98,14 +95,13 @@ __device__ __forceinline__ void fold_row(const RowRegs& R, int r, int lane, Wave
         for (int k = 0; k < 7; k++) W.rk[k] = r8[k];
     }
     const int k = min(lane, 7), off = comp_off(k), len = comp_len(k);
-    uint64_t seg = (vlo >> off) | (off ? (vhi << (64 - off)) : 0ull);   // component k's valid entries as bits
-    seg &= (1ull << len) - 1ull;                                        // (lanes >= 7: none)
+    const uint64_t seg = comp_bits(vlo, vhi, off, len);   // component k's valid entries as bits (lanes >= 7: none)
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     float M = -INFINITY;
     for (uint64_t b = seg; b; b &= b - 1ull) M = fmaxf(M, W.l[off + __builtin_ctzll(b)]);   // the valid entries only: few on real masks
     if (lane < 7) W.M[lane] = M;
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    const int c0 = comp_of(lane), c1 = 6;   // channels 64.. belong to component 6
+    const int c0 = comp_of(lane), c1 = ACT_ATTACK_CELL;   // channels 64.. belong to the last component
     const bool v0 = (vlo >> lane) & 1, v1 = hi && ((vhi >> lane) & 1);
     const float d0 = R.l0 - W.M[c0], d1 = R.l1 - W.M[c1];
     const float E0 = v0 ? expf(d0) : 0.0f, E1 = v1 ? expf(d1) : 0.0f;
@@ -233,9 +229,8 @@ __global__ __launch_bounds__(PT) void k_policy_sample(const float* __restrict__ 
         uint32_t r8[8];
         philox_row(env0 + e, c0 + lane, seed, step, r8);
         if (in) {
-            const int len[7] = {6, 4, 4, 4, 4, 7, 49};
 #pragma unroll
-            for (int k = 0; k < 7; k++) s_out[w][lane * 7 + k] = (long long)(((uint64_t)r8[k] * (uint32_t)len[k]) >> 32);
+            for (int k = 0; k < ACT_COMPONENTS; k++) s_out[w][lane * 7 + k] = draw_uniform(r8[k], ACT_LEN[k]);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
         fold_rows<SAMPLE>(__ballot(in && s_raw != 0), base + c0, lane, logits, mask, nullptr, s_row[w], r8, s_out[w], slp, sent, 0.0f, 0.0f,

@@ -9,6 +9,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "mrts_actions.h"   // A_* action types, the mask channels' layout
 #include "mrts_layout.h"
 
 namespace mrts {
@@ -16,7 +17,6 @@ namespace mrts {
 // ---------------------------------------------------------------------------
 // rts.units.UnitTypeTable() -- VERSION_ORIGINAL (+ UnitType field defaults).
 enum { RESOURCE = 0, BASE, BARRACKS, WORKER, LIGHT, HEAVY, RANGED };
-enum { A_NONE = 0, A_MOVE, A_HARVEST, A_RETURN, A_PRODUCE, A_ATTACK };
 
 __device__ __forceinline__ int ut_cost(int t) { return t == BASE ? 10 : t == BARRACKS ? 5 : (t >= LIGHT ? 2 : 1); }
 __device__ __forceinline__ int ut_hp(int t) { return t == BASE ? 10 : (t == BARRACKS || t == LIGHT || t == HEAVY) ? 4 : 1; }
@@ -162,7 +162,9 @@ __device__ inline void cell_mask(const Grid& gd, int c, int player, const uint32
     uint32_t u = s_unit[c];
     if (u == 0 || u_owner(u) != player || s_act[c] != 0) return;
     auto setb = [&](int b) { m[b >> 5] |= 1u << (b & 31); };
-    const int T = 1, MV = 7, HV = 11, RT = 15, PD = 19, PT = 23, AT = 30;
+    // bit = 1 + channel (bit 0 is the source bit): the components' first bits
+    const int T = 1 + ACT_OFF[ACT_TYPE], MV = 1 + ACT_OFF[ACT_MOVE_DIR], HV = 1 + ACT_OFF[ACT_HARVEST_DIR], RT = 1 + ACT_OFF[ACT_RETURN_DIR],
+              PD = 1 + ACT_OFF[ACT_PRODUCE_DIR], PT = 1 + ACT_OFF[ACT_PRODUCE_TYPE], AT = 1 + ACT_OFF[ACT_ATTACK_CELL];
     setb(0);
     setb(T + A_NONE);
     int t = u_type(u), x = c % gd.W, y = c / gd.W;

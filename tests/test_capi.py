@@ -84,6 +84,49 @@ def test_unbound_calls_fail_loudly():
     assert rc != 0 and b"not bound" in _native.lib().mrts_last_error(h)
 
 
+def test_sampler_and_head_entry_points_check_their_arguments():
+    """The three stand-in samplers and the three action-head entry points share one
+    argument check and return before any launch: MRTS_EINVAL for a null pointer, for
+    num_envs * hw over the 32-bit row bound (2^20 x 2048 = 2^31) and, for the stand-in
+    samplers, for an `actions` address of 8 mod 16 (their 16-byte stores); MRTS_OK for
+    num_envs == 0.  No pointer is dereferenced on the host, so plain addresses do."""
+    from gym_microrts import _native
+
+    lib = _native.lib()
+    OK, EINVAL, P = _native.MRTS_OK, -1, 4096   # P: a non-null, 16-byte aligned address
+
+    def group(n, hw, actions=P, mask=P, source=P):
+        return lib.mrts_sample_actions_src_group(None, (_native.SampleSeg * 1)(_native.SampleSeg(mask, source, n, hw, 0, actions)), 1, 1, 0)
+
+    # fn(n, hw, **pointers by name): every pointer argument defaults to P
+    calls = {
+        "sample": (lambda n, hw, mask=P, actions=P: lib.mrts_sample_actions(None, mask, n, hw, 0, 1, 0, actions), ["mask", "actions"]),
+        "sample_src": (lambda n, hw, mask=P, source=P, actions=P: lib.mrts_sample_actions_src(None, mask, source, n, hw, 0, 1, 0, actions),
+                       ["mask", "source", "actions"]),
+        "sample_src_group": (group, ["mask", "source", "actions"]),
+        "policy_sample": (lambda n, hw, logits=P, mask=P, source=P, actions=P, logprob=P, entropy=P:
+                          lib.mrts_policy_sample(None, logits, mask, source, n, hw, 0, 1, 0, actions, logprob, entropy),
+                          ["logits", "mask", "source", "actions", "logprob", "entropy"]),
+        "policy_evaluate": (lambda n, hw, logits=P, mask=P, source=P, actions=P, logprob=P, entropy=P:
+                            lib.mrts_policy_evaluate(None, logits, mask, source, n, hw, actions, logprob, entropy),
+                            ["logits", "mask", "source", "actions", "logprob", "entropy"]),
+        "policy_evaluate_backward": (lambda n, hw, logits=P, mask=P, source=P, actions=P, g_lp=P, g_ent=P, grad=P:
+                                     lib.mrts_policy_evaluate_backward(None, logits, mask, source, n, hw, actions, g_lp, g_ent, grad),
+                                     ["logits", "mask", "source", "actions", "g_lp", "g_ent", "grad"]),
+    }
+    assert lib.mrts_sample_actions_src_group(None, None, 1, 1, 0) == EINVAL
+    for name, (fn, pointers) in calls.items():
+        for ptr in pointers:
+            assert fn(2, 256, **{ptr: None}) == EINVAL, (name, ptr)
+        assert fn(1 << 20, 2048) == EINVAL, name   # n * hw = 2^31: just over the bound
+        assert fn(0, 256) == OK, name
+        if name.startswith("sample"):
+            assert fn(2, 256, actions=P + 8) == EINVAL, name
+            assert fn(0, 256, actions=P + 8) == EINVAL, name
+    # the action head's sampler takes any int64-aligned actions (per-element path)
+    assert calls["policy_sample"][0](0, 256, actions=P + 8) == OK
+
+
 def test_map_loader_matches_python_parser():
     """C++ PhysicalGameState loader vs the oracle harness' python parser on every
     authored map: same size and unit count (workspace size reflects maps)."""
