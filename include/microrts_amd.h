@@ -111,7 +111,9 @@ int mrts_get_masks(mrts_vec *h, void *stream, int32_t *mask, int32_t *source);
  * the bytes a following mrts_get_masks would write -- into mask [N][H*W][78]
  * int32 and source [N][H*W] int32, in the same kernel pass.  `source` may be
  * the buffer mrts_step reads its rows from (each game reads its own rows
- * before it rewrites them).  NULL, NULL unbinds. */
+ * before it rewrites them).  NULL, NULL unbinds.  While bound, the mask buffer
+ * is the engine's between steps; binding again (also the same pointers) tells
+ * it that the buffer's contents are no longer its own (mrts_set_mask_delta). */
 int mrts_bind_mask_outputs(mrts_vec *h, int32_t *mask, int32_t *source);
 
 /* Bot fusion (default on).  A bot's getAction(1, gs) reads only the state
@@ -125,6 +127,22 @@ int mrts_bind_mask_outputs(mrts_vec *h, int32_t *mask, int32_t *source);
  * when no env has a bot as player 0 (MicroRTSBotVecEnv), the map has more than
  * 64 cells and its two LDS regions fit one workgroup (160 KB); on = 0 launches the bot kernel at every step. */
 int mrts_set_bot_fusion(mrts_vec *h, int32_t on);
+
+/* Delta masks (default on).  getMasks(0) sets no channel of a cell that holds no
+ * idle unit of the player, so all but about 1 % of the bound mask rows are zero
+ * and stay zero from tick to tick.  With delta masks, a step that follows a
+ * launch which wrote every row of the bound buffers (mrts_reset, mrts_load_state,
+ * a step, or mrts_get_masks into exactly the bound pointers) stores only the mask
+ * rows that can differ from what the buffer holds: the source rows of the state
+ * it loads (zeroed unless still source rows) and the source rows of the state it
+ * leaves.  `source` is still written in full.  The bytes in the buffers are the
+ * same either way, PROVIDED nobody else writes the mask buffer: while masks are
+ * bound the engine owns that buffer between steps (callers read or copy it, as
+ * the reference's rollout loop does).  A caller that wrote into it calls
+ * mrts_bind_mask_outputs again (the same pointers will do) -- the next step then
+ * writes every row -- or turns delta masks off.  on = 0: every step writes every
+ * row. */
+int mrts_set_mask_delta(mrts_vec *h, int32_t on);
 
 /* step_async + JNIGridnetVecClient.gameStep (vec_env.py:968-984, 1002):
  * actions [N][H*W][7] int64 (device), source [N][H*W] int32 = the source

@@ -181,7 +181,42 @@ struct mrts_vec {
     // bot fusion (mrts_set_bot_fusion): k_step decides the next tick's bot actions
     int fuse = 1;             // requested
     bool bots_ready = false;  // the bot decisions for the current state are in botpa / aa
+    // delta masks (mrts_set_mask_delta): k_step stores only the mask rows that can differ
+    // from what the bound buffer holds, which needs masks_synced: every row of next_mask
+    // is getMasks(0) of the stored state (parked games: zeros).  Every entry point that
+    // changes the game state or the binding, and its effect on masks_synced:
+    //   mrts_bind_workspace      cleared (new state memory)
+    //   mrts_bind_mask_outputs   cleared, also for the same pointers: the way a caller who wrote
+    //                            into the buffer hands it back
+    //   mrts_reset               set (k_reset writes every game's rows)
+    //   mrts_step / _weighted / mrts_step_group
+    //                            dense step: set; delta step: stays set (it ran because it was set)
+    //   mrts_get_masks           set when called with exactly the bound pointers (k_masks writes
+    //                            every row); cleared when only one of the two is the bound one
+    //   mrts_load_state          cleared once the state copy is queued, set by its outputs launch
+    //   mrts_reset_games / mrts_park_games
+    //                            left alone: k_reset writes the listed games' rows in full (zeros
+    //                            for parked ones), the others are untouched; a parked game's
+    //                            k_step returns before any write and its rows stay zero
+    //   mrts_add_map, mrts_set_reward_weight, mrts_set_bot_fusion, mrts_set_mask_delta, mrts_save_state,
+    //   mrts_get_raw_obs, mrts_render, mrts_game_stats, mrts_error_flags
+    //                            no effect (neither the state nor the buffer changes)
+    // and any of the launches above that fails while masks are bound clears it.
+    int mask_delta = 1;          // requested
+    bool masks_synced = false;
 };
+
+// the launches that write the bound mask buffers report here: `dense` = every game's rows
+static void masks_written(mrts_vec *h, hipError_t e, bool dense) {
+    if (!h->next_mask) return;
+    if (e) h->masks_synced = false;
+    else if (dense) h->masks_synced = true;
+}
+// delta needs a bit per cell and view in one register of the lane that owns the cell: at
+// most 16 cells per lane of the narrowest step workgroup (every map mrts_create accepts)
+static bool delta_ok(const mrts_vec *h) {
+    return h->mask_delta && h->masks_synced && h->next_mask && h->HW <= 16 * mrts_engine_step_nt(h->HW, 0);
+}
 
 static int fail(mrts_vec *h, int code, const std::string &msg) {
     if (h) h->err = msg;
@@ -298,6 +333,7 @@ int mrts_bind_workspace(mrts_vec *h, void *dev, void *stream) {
     if (((uintptr_t)dev & 255u) != 0) return fail(h, MRTS_EINVAL, "workspace must be 256-byte aligned");
     hipStream_t s = (hipStream_t)stream;
     h->bots_ready = false;
+    h->masks_synced = false;
     h->ws = (unsigned char *)dev;
     const int nm = (int)h->maps.size();
     std::vector<int4> mc((size_t)nm * h->HW);
@@ -378,6 +414,7 @@ static hipError_t step_launch(mrts_vec *h, EngineParams &p, hipStream_t s) {
     p.fuse_bots = fused(h) ? 1 : 0;
     if (!e) e = mrts_engine_step(&p, s);
     h->bots_ready = p.fuse_bots != 0;
+    masks_written(h, e, !p.mask_delta);
     return e;
 }
 
@@ -403,6 +440,12 @@ int mrts_set_bot_fusion(mrts_vec *h, int32_t on) {
     return MRTS_OK;
 }
 
+int mrts_set_mask_delta(mrts_vec *h, int32_t on) {
+    if (!h) return fail(h, MRTS_EINVAL, "set_mask_delta: null handle");
+    h->mask_delta = on ? 1 : 0;   // masks_synced stays: a dense step keeps the buffer in sync too
+    return MRTS_OK;
+}
+
 int mrts_reset(mrts_vec *h, void *stream, void *obs) {
     if (!bound(h) || !obs) return fail(h, MRTS_ESTATE, "reset: workspace not bound or obs null");
     EngineParams p = h->base;
@@ -411,6 +454,7 @@ int mrts_reset(mrts_vec *h, void *stream, void *obs) {
     p.src_out = h->next_src;
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = mrts_engine_reset(&p, s, nullptr, nullptr, 0);
+    masks_written(h, e, true);
     if (!e) e = bots_after_reset(h, s, nullptr, 0);
     return e ? hip_fail(h, e, "reset launch") : MRTS_OK;
 }
@@ -421,6 +465,8 @@ int mrts_get_masks(mrts_vec *h, void *stream, int32_t *mask, int32_t *source) {
     p.mask = mask;
     p.src_out = source;
     hipError_t e = mrts_engine_masks(&p, (hipStream_t)stream);
+    if (mask == h->next_mask && source == h->next_src) masks_written(h, e, true);
+    else if (mask == h->next_mask || source == h->next_src) h->masks_synced = false;   // half the binding: not the engine's rows
     return e ? hip_fail(h, e, "masks launch") : MRTS_OK;
 }
 
@@ -440,6 +486,7 @@ static EngineParams step_params(const mrts_vec *h, const mrts_step_io &io) {
     }
     p.mask = h->next_mask;
     p.src_out = h->next_src;
+    p.mask_delta = delta_ok(h) ? 1 : 0;
     return p;
 }
 
@@ -589,6 +636,8 @@ int mrts_step_group(mrts_vec *const *hs, int32_t n, void *stream, const mrts_ste
         hipError_t e = mrts_engine_step_group(grp, m, s, (policy & MRTS_GROUP_BOTS_FIRST) != 0);
         // not atomic: members of launches 0..l-1 have stepped, those of l.. have not
         // (include/microrts_amd.h); each member's bot state follows its own launch
+        for (int i = 0; i < n; i++)
+            if (launch_of[i] == l) masks_written(hs[i], e, !ps[i].mask_delta);
         if (e) return group_fail(hs, first, MRTS_EHIP, std::string("step_group launch: ") + hipGetErrorString(e));
         for (int i = 0; i < n; i++)
             if (launch_of[i] == l) hs[i]->bots_ready = ps[i].fuse_bots != 0;
@@ -627,6 +676,7 @@ int mrts_reset_games(mrts_vec *h, void *stream, const int32_t *games, const int3
     p.mask = h->next_mask;
     p.src_out = h->next_src;
     e = mrts_engine_reset(&p, s, dg, dg + count, count);
+    masks_written(h, e, false);   // the listed games' rows only
     if (!e) e = bots_after_reset(h, s, dg, count);
     if (e) return hip_fail(h, e, "reset_games launch");
     // the host staging vector must outlive the copy
@@ -692,6 +742,7 @@ int mrts_park_games(mrts_vec *h, void *stream, const int32_t *games, int32_t cou
     p.src_out = h->next_src;
     e = mrts_engine_reset(&p, s, dg, dg + count, count);
     if (!e) e = hipStreamSynchronize(s);
+    masks_written(h, e, false);   // the listed games' rows only (zeros)
     return e ? hip_fail(h, e, "park_games launch") : MRTS_OK;
 }
 
@@ -752,6 +803,7 @@ int mrts_bind_mask_outputs(mrts_vec *h, int32_t *mask, int32_t *source) {
     if (mask && ((uintptr_t)mask & 15u)) return fail(h, MRTS_EINVAL, "bind_mask_outputs: mask must be 16-byte aligned");
     h->next_mask = mask;
     h->next_src = source;
+    h->masks_synced = false;   // whatever the buffers hold is the caller's
     return MRTS_OK;
 }
 
@@ -857,6 +909,7 @@ int mrts_load_state(mrts_vec *h, void *stream, const void *src, void *obs) {
     if (!e) e = hipStreamSynchronize(s);
     if (e) return hip_fail(h, e, "load_state header");
     e = hipMemcpyAsync(h->ws, (const unsigned char *)src + hdr.size(), h->total, hipMemcpyDeviceToDevice, s);
+    h->masks_synced = false;   // the state is another one from here on, even if the copy failed
     if (e) return hip_fail(h, e, "load_state copy");
     // the host mirrors only once the workspace copy is queued: a failed copy leaves them as they were
     std::memcpy(h->game_map.data(), hdr.data() + sizeof sh, (size_t)h->ngames * sizeof(int32_t));
@@ -868,6 +921,7 @@ int mrts_load_state(mrts_vec *h, void *stream, const void *src, void *obs) {
     p.mask = h->next_mask;
     p.src_out = h->next_src;
     e = mrts_engine_outputs(&p, s);
+    masks_written(h, e, true);
     return e ? hip_fail(h, e, "load_state outputs launch") : MRTS_OK;
 }
 

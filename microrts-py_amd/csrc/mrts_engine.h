@@ -57,6 +57,9 @@ struct EngineParams {
     uint8_t *done;          // [N][6]
     int32_t *mask;          // [N][HW][78]: k_masks output; k_step / k_reset write the
     int32_t *src_out;       // [N][HW]      next tick's masks here when non-null
+    int mask_delta;         // k_step: `mask` holds getMasks(0) of the state the step loads (mrts_capi.cpp keeps
+                            // track), so only the rows that can differ are stored: the source rows of the loaded
+                            // and of the final state (mrts_set_mask_delta); src_out is written in full either way
     // optional fused step_wait outputs (vec_env.py:1057): reward = raw @ rw
     // (float64, k = 0..5 in order; channels 1..5 zeroed when !shaping) and done[:,0]
     double *reward;         // [N] or null

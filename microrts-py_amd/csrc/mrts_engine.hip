@@ -14,7 +14,9 @@
 // conflict resolution, execution of ready actions in LinkedHashMap order) run
 // on lane 0 over compact ballot-built lists, which hold only the few units
 // that act this tick.  Outputs are written with 16-byte stores from compact
-// per-cell bit words in LDS (one-hot obs: 1 word/cell, mask: 3 words/cell).
+// per-cell bit words in LDS (one-hot obs: 1 word/cell, mask: 3 words/cell); of the
+// bound mask rows the step stores only those that can differ from the last tick's
+// (delta masks, stream_masks_delta).
 // A step launch takes a StepGroup: one or more engines (map-size buckets) cut
 // into grid segments, bot games first (mrts_step_group).
 // In this unit: the game step, the output streams (reset / masks / outputs / raw obs),
@@ -392,12 +394,20 @@ __device__ __forceinline__ void onehot_words(const EngineParams& p, const Lds& L
         }
     }
 }
-__device__ __forceinline__ void mask_words(const EngineParams& p, const Lds& L, const Game& G, int c, int res0, int res1) {
+// Delta masks (EngineParams::mask_delta): a row's third word carries, above its 15
+// mask bits (a row is 79 of the words' 96 bits), whether the row is stored at all.
+// step_game presets the bit for the source rows of the state it loaded, mask_words
+// adds the source rows of the final state, stream_masks_delta stores the marked rows.
+// The dense stream never reads the bit.
+constexpr uint32_t MASK_ROW_STORE = 1u << 31;
+__device__ __forceinline__ void mask_words(const EngineParams& p, const Lds& L, const Game& G, int c, int res0, int res1,
+                                           bool delta = false) {
     const int HW = p.HW;
     const Grid gd{p.W, p.H, HW};
     for (int v = 0; v < G.nviews; v++) {
         uint32_t m[3];
         cell_mask(gd, c, v, L.unit, L.act, L.wall, v == 0 ? res0 : res1, m);
+        if (delta) m[2] |= (L.outm[3 * (v * HW + c) + 2] & MASK_ROW_STORE) | ((m[0] & 1u) ? MASK_ROW_STORE : 0u);
         L.outm[3 * (v * HW + c)] = m[0];
         L.outm[3 * (v * HW + c) + 1] = m[1];
         L.outm[3 * (v * HW + c) + 2] = m[2];
@@ -486,6 +496,36 @@ __device__ __forceinline__ void stream_masks(const EngineParams& p, const Lds& L
     }
 }
 
+// phase B's mask rows with delta masks: only the rows marked MASK_ROW_STORE (some tens
+// of a game's 2 HW; the others hold zeros already).  Each wave scans 64 rows per trip,
+// one per lane, and stores the marked ones together: lanes 0..38 two channels each, one
+// 8-byte store per row (a row starts at a multiple of 312 bytes: 8-byte aligned for
+// every map size).  Lanes t0 .. t0 + nt as the other streams; nt is a multiple of 64.
+__device__ __forceinline__ void stream_masks_delta(const EngineParams& p, const Lds& L, const Game& G, int t0, int nt) {
+    static_assert(MRTS_MASK_CH == 78, "mask row layout");
+    typedef int v2i __attribute__((ext_vector_type(2)));
+    const int rows = G.nviews * p.HW, lane = t0 & 63;
+    const uint32_t* mw = L.outm;
+    int32_t* out = p.mask + (size_t)G.env0 * p.HW * MRTS_MASK_CH;
+    for (int base = t0 - lane; base < rows; base += nt) {   // wave-uniform
+        const int r = base + lane;
+        unsigned long long m = __ballot(r < rows && (mw[3 * r + 2] & MASK_ROW_STORE) != 0);
+        while (m) {
+            const int rr = base + __builtin_ctzll(m);
+            m &= m - 1;
+            if (lane < MRTS_MASK_CH / 2) {
+                // channels 2 lane, 2 lane + 1 = bits b, b + 1 of the row's words (bit 0 = source), b odd
+                const int b = 2 * lane + 1;
+                const uint32_t w0 = mw[3 * rr], w1 = mw[3 * rr + 1], w2 = mw[3 * rr + 2] & ~MASK_ROW_STORE;
+                const uint32_t lo = b < 32 ? w0 : b < 64 ? w1 : w2, hi = b < 32 ? w1 : b < 64 ? w2 : 0u;
+                const uint32_t bits = (uint32_t)((((uint64_t)hi << 32) | lo) >> (b & 31));
+                const v2i v = {(int)(bits & 1u), (int)((bits >> 1) & 1u)};
+                *reinterpret_cast<v2i*>(out + (size_t)rr * MRTS_MASK_CH + 2 * lane) = v;
+            }
+        }
+    }
+}
+
 // All outputs of one game once its state is final.  Phase A (lane per cell):
 // every view's one-hot word and, with `masks`, its getMasks(0) 79-bit word
 // (+ the source channel, written straight out) into LDS; one barrier; phase B:
@@ -505,19 +545,22 @@ __device__ __forceinline__ void stream_masks(const EngineParams& p, const Lds& L
 // words (and, under partial observability, the sight disks) are computed, so a
 // game's first bytes leave one phase earlier and the obs words are built while the
 // mask stores drain; one more barrier before the obs stream.
+// `delta` (k_step with EngineParams::mask_delta): the mask rows' third words arrive
+// preset with MASK_ROW_STORE and only the marked rows are stored (stream_masks_delta).
 template <int NT, int P, typename OT>
 __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L, const Game& G, bool obs, bool masks, int res0,
-                                             int res1, int skip = 0, int* early_cnt = nullptr) {
+                                             int res1, int skip = 0, int* early_cnt = nullptr, bool delta = false) {
     const int HW = p.HW;
     if (skip == 0 && obs && masks) {
         const int nw = HW / 32 + 1;
-        for (int c = threadIdx.x; c < HW; c += NT) mask_words(p, L, G, c, res0, res1);
+        for (int c = threadIdx.x; c < HW; c += NT) mask_words(p, L, G, c, res0, res1, delta);
         if (P == 31)
             for (int i = threadIdx.x; i < 2 * nw; i += NT) L.vis[i] = 0;
         __syncthreads();
         MRTS_STAMP(8, threadIdx.x == 0);
         __builtin_amdgcn_s_setprio(0);
-        stream_masks(p, L, G, threadIdx.x, NT);
+        if (delta) stream_masks_delta(p, L, G, threadIdx.x, NT);
+        else stream_masks(p, L, G, threadIdx.x, NT);
         if (P == 31) {   // compute_vis's sight disks (cleared above)
             for (int c = threadIdx.x; c < HW; c += NT) {
                 const uint32_t u = L.unit[c];
@@ -536,7 +579,7 @@ __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L
     const int a0 = early_cnt ? skip : 0;   // phase A's first lane
     for (int c = (int)threadIdx.x - a0; c < HW; c += NT - a0) {
         if (obs) onehot_words<P>(p, L, G, c);
-        if (masks) mask_words(p, L, G, c, res0, res1);
+        if (masks) mask_words(p, L, G, c, res0, res1, delta);
     }
     if (early_cnt) {   // the streaming waves' own meeting point (wave 0 never arrives)
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -558,7 +601,8 @@ __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L
     __builtin_amdgcn_s_setprio(0);
     const int t0 = (int)threadIdx.x - skip, nt = NT - skip;
     if (obs) stream_obs<P, OT>(p, L, G, t0, nt);
-    if (masks) stream_masks(p, L, G, t0, nt);
+    if (masks && delta) stream_masks_delta(p, L, G, t0, nt);
+    else if (masks) stream_masks(p, L, G, t0, nt);
     MRTS_STAMP_MAX(9, (threadIdx.x & 63) == 0);
 }
 
@@ -1112,12 +1156,17 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     //   a pending produce is over its owner's budget; + the target positions the
     //   agent's move / produce rows claim (step 2a)
     int units = 0;   // player 0's units + player 1's << 16 (SC_HAS)
-    // per cell: unit counts, pending reservations / produce budgets; returns the
-    // view whose agent row the cell's idle unit may take (-1: none)
-    auto cell_pass = [&](int c, uint32_t u) {
+    // delta masks: bit 2 k + v = this lane's k-th cell was a source row of view v in the
+    // loaded state (cell_mask's first test), i.e. the bound mask buffer holds a row there
+    // (at most 16 cells per lane: mrts_capi.cpp delta_ok)
+    uint32_t was_src = 0;
+    // per cell (the lane's k-th): unit counts, pending reservations / produce budgets;
+    // returns the view whose agent row the cell's idle unit may take (-1: none)
+    auto cell_pass = [&](int c, uint32_t u, int k) {
         const int ow = u_owner(u);
         if (u != 0 && (ow == 0 || ow == 1)) units += ow ? 1 << 16 : 1;
         const uint32_t pa = L.act[c];
+        if (u != 0 && pa == 0 && ow >= 0 && ow < G.nviews) was_src |= 1u << ((2 * k + ow) & 31);
         if (pa) {
             const int code = act_code(pa), ty = code_type(code);
             if (ty == A_MOVE || ty == A_PRODUCE) {
@@ -1160,9 +1209,9 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
         return CAND | (lg ? LEGAL : 0u) | (uint32_t)code;
     };
     if (!pf_wide) {   // one cell per lane (maps of <= NT cells) or the unprefetched path
-        for (int c = threadIdx.x; c < HW; c += NT) {
+        for (int c = threadIdx.x, k = 0; c < HW; c += NT, k++) {
             const uint32_t u = L.unit[c];
-            const int v = cell_pass(c, u);
+            const int v = cell_pass(c, u, k);
             uint32_t nw = 0;
             if (v >= 0 && (c == (int)threadIdx.x ? src_pre[v] : p.src[(size_t)(G.env0 + v) * HW + c])) nw = decode_row(c, v, u_owner(u));
             L.aux[c] = nw;
@@ -1181,7 +1230,7 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
             int e = -1;
             if (c < HW) {
                 const uint32_t u = L.unit[c];
-                const int v = cell_pass(c, u);
+                const int v = cell_pass(c, u, k);
                 if (v >= 0 && ((L.aux[c] >> v) & 1u)) e = c | (v << 16);
                 L.aux[c] = 0;
             }
@@ -1441,6 +1490,14 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     // kernel's code.
     const bool early = early_layout && botg;
     unsigned char* const tail = smem + fb_tail_offset(HW, p.W, NT, early_layout);
+    // Delta masks: the rows the bound buffer holds from the last tick (the loaded state's
+    // source rows) are marked in the mask words' region -- dead scratch lists, or a bot
+    // game's own region -- by the lane that met the cell in the decode; phase A reads the
+    // mark back on the same lane, or, on the early path, behind the barriers below.
+    const bool delta = p.mask != nullptr && p.mask_delta != 0;
+    if (delta)
+        for (int c = threadIdx.x, k = 0; c < HW; c += NT, k++)
+            for (int v = 0; v < G.nviews; v++) L.outm[3 * (v * HW + c) + 2] = ((was_src >> (2 * k + v)) & 1u) ? MASK_ROW_STORE : 0u;
     if (early) {
         __syncthreads();
         bot_setup_workgroup<NT>(p, smem, tail, L.wall);
@@ -1448,7 +1505,7 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
         MRTS_STAMP(14, threadIdx.x == 0);
     }
     if (!early || threadIdx.x >= 64)
-        emit_outputs<NT, P, OT>(p, L, G, true, p.mask != nullptr, res0, res1, botg ? 64 : 0, early ? early_cnt : nullptr);
+        emit_outputs<NT, P, OT>(p, L, G, true, p.mask != nullptr, res0, res1, botg ? 64 : 0, early ? early_cnt : nullptr, delta);
     if (FB && botg && threadIdx.x < 64) {
         if (early) __builtin_amdgcn_s_setprio(3);   // the latency-bound bot wave first; the streaming waves are memory-bound
         bots::bot_game<true>(p, g - p.nsp_games, 1, smem, L.sc, pf_ok, pf.aa, pf.aa2, tail, L.wall, early);

@@ -201,10 +201,19 @@ class MicroRTSGridModeVecEnv:
         obs_dtype=None,
         eager_masks=True,
         bot_fusion=True,
+        mask_delta=None,
         game_offset=0,
         _ai1s=None,
         _extra_maps=(),
     ):
+        """mask_delta (eager masks only; None = on, unless the environment variable
+        MICRORTS_AMD_MASK_DELTA=0): step() stores only the mask rows that can differ
+        from the last tick's -- the source cells before and after the tick -- instead of
+        all N * H*W of them (mrts_set_mask_delta).  The tensor get_action_mask() returns
+        holds the same bytes either way, but while masks are eager it belongs to the
+        engine between steps: read or copy it, do not write into it.  A caller that did
+        write into it calls mrts_bind_mask_outputs again (the next step then rewrites
+        every row) or passes mask_delta=False."""
         # vec_env.py:110-127
         self.num_selfplay_envs = num_selfplay_envs
         self.num_bot_envs = num_bot_envs
@@ -317,6 +326,11 @@ class MicroRTSGridModeVecEnv:
         # the same pass (mrts_set_bot_fusion; outputs identical either way)
         self.bot_fusion = bool(bot_fusion)
         _native.check(_native.lib().mrts_set_bot_fusion(self._h, int(self.bot_fusion)), self._h, "set_bot_fusion")
+        # delta masks: a step stores only the mask rows that can have changed (mrts_set_mask_delta)
+        if mask_delta is None:
+            mask_delta = os.environ.get("MICRORTS_AMD_MASK_DELTA", "1").strip() != "0"
+        self.mask_delta = bool(mask_delta)
+        _native.check(_native.lib().mrts_set_mask_delta(self._h, int(self.mask_delta)), self._h, "set_mask_delta")
 
         # computed properties (vec_env.py:230-254)
         self.action_space_dims = [6, 4, 4, 4, 4, len(self.utt["unitTypes"]), 7 * 7]
@@ -861,6 +875,8 @@ class MicroRTSMixedMapVecEnv:
       obs  = env.reset()                       # list over buckets
       mask = env.get_action_mask()             # list over buckets
       obs, rew, done, infos = env.step(actions)  # actions: list over buckets
+
+    Keyword arguments (mask_delta among them) go to every bucket's engine.
     """
 
     def __init__(self, buckets, concurrent=False, group_policy="default", **common):
@@ -1001,7 +1017,7 @@ class MicroRTSSizeCyclingVecEnv:
 
     def __init__(self, num_selfplay_envs, num_bot_envs, ai2s=[], map_paths=["maps/16x16/basesWorkers16x16.xml"], cycle_maps=[],
                  max_steps=2000, partial_obs=False, reward_weight=np.array([0.0, 1.0, 0.0, 0.0, 0.0, 5.0]), device=None,
-                 obs_dtype=None):
+                 obs_dtype=None, mask_delta=None):
         self.num_selfplay_envs, self.num_bot_envs = num_selfplay_envs, num_bot_envs
         self.num_envs = num_selfplay_envs + num_bot_envs
         root = os.path.join(gym_microrts.__path__[0], "microrts")
@@ -1023,7 +1039,8 @@ class MicroRTSSizeCyclingVecEnv:
             maps_i = [m if self._size_of[m] == sz else own[0] for m in per_env]   # placeholders are parked at reset
             self.envs.append(MicroRTSGridModeVecEnv(num_selfplay_envs, num_bot_envs, partial_obs=partial_obs, max_steps=max_steps,
                                                     ai2s=ai2s, map_paths=maps_i, reward_weight=reward_weight, device=device,
-                                                    return_tensors=True, obs_dtype=obs_dtype, _extra_maps=own))
+                                                    return_tensors=True, obs_dtype=obs_dtype, mask_delta=mask_delta,
+                                                    _extra_maps=own))
         self.device = self.envs[0].device
         self.reward_weight = reward_weight
 
