@@ -198,14 +198,15 @@ def policy(net, obs, mask, hw, action=None):
 
 def policy_fused(net, obs, mask, source, action=None, seed=0, step=0):
     """policy() over gym_microrts.policy_head: mask / source are the engine's int32
-    tensors (or the rollout buffer's copies of them).  A component without a valid
+    tensors (or the rollout buffer's copies of them), or mask is the packed form
+    ([N, HW, 3] int32, get_action_mask_packed()) and source is None.  A component without a valid
     entry contributes 0 to the log-prob and the entropy (the reference's float32
     result), where policy()'s log_softmax gives -log(len) and log(len)."""
     logits, value = net(obs)
     if action is None:
         action, logp, ent = policy_head.sample(logits, mask, source, seed=seed, step=step)
     else:
-        logp, ent = policy_head.evaluate(logits, mask, source, action)
+        logp, ent = policy_head.evaluate(logits, mask, source, actions=action)
     return action, logp, ent, value
 
 
@@ -216,15 +217,22 @@ def bot_list(n):
 
 
 def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, updates=2, api="numpy", minibatches=4,
-        epochs=2, seed=1, device="cuda", log=print, max_steps=2000, head="torch", keep_first_rollout=False):
+        epochs=2, seed=1, device="cuda", log=print, max_steps=2000, head="torch", keep_first_rollout=False, masks="dense"):
     """head: "torch" or "fused" (policy_fused; --api tensor only).  keep_first_rollout: the
     returned stats carry "first_rollout" -- the first rollout's buffers and the weights
-    that acted in it."""
+    that acted in it.  masks: "dense", or "packed" (--head fused only): the rollout buffer
+    holds get_action_mask_packed()'s 12-byte rows instead of the 316 bytes of mask +
+    source, and the update gathers and evaluates from them."""
     if head not in ("torch", "fused"):
         raise ValueError(f"head must be 'torch' or 'fused', not {head!r}")
     if head == "fused" and api != "tensor":
         raise ValueError("--head fused needs --api tensor: the head reads the engine's device masks")
+    if masks not in ("dense", "packed"):
+        raise ValueError(f"masks must be 'dense' or 'packed', not {masks!r}")
+    if masks == "packed" and head != "fused":
+        raise ValueError("--masks packed needs --head fused: only the fused head reads packed masks")
     fused = head == "fused"
+    packed = masks == "packed"
     torch.manual_seed(seed)
     np.random.seed(seed)
     dev = torch.device(device)
@@ -253,8 +261,11 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
     opt = torch.optim.Adam(net.parameters(), lr=2.5e-4, eps=1e-5)
     buf_obs = torch.zeros((num_steps, n, h, w, planes), device=dev)
     # the fused head reads the engine's int32 masks, and the source channel next to them
-    buf_mask = torch.zeros((num_steps, n, hw, sum(NVEC)), device=dev, dtype=torch.int32 if fused else torch.float32)
-    buf_src = torch.zeros((num_steps, n, hw), device=dev, dtype=torch.int32) if fused else None
+    if packed:   # the source channel is bit 0 of the packed words: no buf_src
+        buf_mask = torch.zeros((num_steps, n, hw, 3), device=dev, dtype=torch.int32)
+    else:
+        buf_mask = torch.zeros((num_steps, n, hw, sum(NVEC)), device=dev, dtype=torch.int32 if fused else torch.float32)
+    buf_src = torch.zeros((num_steps, n, hw), device=dev, dtype=torch.int32) if fused and not packed else None
     buf_act = torch.zeros((num_steps, n, hw, len(NVEC)), dtype=torch.long, device=dev)
     buf_logp, buf_rew, buf_done, buf_val = (torch.zeros((num_steps, n), device=dev) for _ in range(4))
 
@@ -276,12 +287,15 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
             with torch.no_grad():
                 if ref_calls:   # ppo_gridnet.py:466
                     buf_mask[t] = torch.tensor(envs.get_action_mask()).to(dev)
+                elif packed:
+                    buf_mask[t] = envs.get_action_mask_packed()
                 elif fused:
                     buf_mask[t], buf_src[t] = envs.get_action_mask(), envs.source_unit_mask
                 else:
                     buf_mask[t] = as_dev(envs.get_action_mask())
                 if fused:
-                    a, logp, _, v = policy_fused(net, next_obs, buf_mask[t], buf_src[t], seed=seed, step=update * num_steps + t)
+                    a, logp, _, v = policy_fused(net, next_obs, buf_mask[t], None if packed else buf_src[t], seed=seed,
+                                                 step=update * num_steps + t)
                 else:
                     a, logp, _, v = policy(net, next_obs, buf_mask[t], hw)
             buf_act[t], buf_logp[t], buf_val[t] = a, logp, v
@@ -306,7 +320,7 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
         rollout_s += time.time() - tr
         if keep_first_rollout and update == 0:
             first_rollout.update(obs=buf_obs.clone(), mask=buf_mask.clone(), actions=buf_act.clone(), logprob=buf_logp.clone(),
-                                 source=buf_src.clone() if fused else None)
+                                 source=buf_src.clone() if buf_src is not None else None)
         with torch.no_grad():   # GAE (gamma 0.99, lambda 0.95)
             _, last_v = net(next_obs)
             adv = torch.zeros_like(buf_rew)
@@ -319,7 +333,7 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
             ret = adv + buf_val
         B = num_steps * n
         flat = [x.reshape((B,) + x.shape[2:]) for x in (buf_obs, buf_mask, buf_act, buf_logp, adv, ret, buf_val)]
-        flat_src = buf_src.reshape(B, hw) if fused else None
+        flat_src = buf_src.reshape(B, hw) if buf_src is not None else None
         mb = max(1, B // minibatches)
         for _ in range(epochs):
             perm = torch.randperm(B, device=dev)
@@ -328,7 +342,7 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
                 o, m, a, lp0, ad, rt, v0 = (x[idx] for x in flat)
                 ad = (ad - ad.mean()) / (ad.std() + 1e-8)
                 if fused:
-                    _, lp, ent, v = policy_fused(net, o, m, flat_src[idx], action=a)
+                    _, lp, ent, v = policy_fused(net, o, m, None if packed else flat_src[idx], action=a)
                 else:
                     _, lp, ent, v = policy(net, o, m, hw, action=a)
                 ratio = (lp - lp0).exp()
@@ -451,7 +465,8 @@ if __name__ == "__main__":
     ap.add_argument("--api", choices=["numpy", "hybrid", "tensor"], default="numpy")
     ap.add_argument("--max-steps", type=int, default=2000)
     ap.add_argument("--head", choices=["torch", "fused"], default="torch")
+    ap.add_argument("--masks", choices=["dense", "packed"], default="dense")
     a = ap.parse_args()
     out = run(a.num_selfplay_envs, a.num_bot_envs, a.partial_obs, a.num_steps, a.updates, a.api, a.minibatches,
-              log=lambda s: print(json.dumps(s), flush=True), max_steps=a.max_steps, head=a.head)
+              log=lambda s: print(json.dumps(s), flush=True), max_steps=a.max_steps, head=a.head, masks=a.masks)
     print(json.dumps(out))

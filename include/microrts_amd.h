@@ -292,6 +292,46 @@ int mrts_policy_evaluate_backward(void *stream, const float *logits, const int32
                                   int32_t hw, const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
                                   float *grad_logits);
 
+/* Packed masks: getMasks' 79-bit word per cell as it is, the form a rollout buffer
+ * can afford to keep (12 bytes a row against the dense form's 316).
+ *   packed [N][H*W][3] int32, holding uint32 bit patterns;
+ *   word j, bit b of row (env, cell) is bit 32 j + b of the 79-bit word;
+ *   bit 0 is the source channel, bit ch + 1 is mask channel ch;
+ *   bits 79..95 are zero in everything this library writes, and every reader
+ *   ignores them;
+ *   a row is 12 bytes, so packed buffers need 4-byte alignment only.
+ * The handle-free calls below take num_envs * hw up to 2^31 - 257 rows, as the
+ * samplers do, and return MRTS_EINVAL before any launch for a null pointer, hw < 1,
+ * num_envs < 0 or more rows; they run on `stream`, allocate and synchronise nothing.
+ *
+ * mrts_get_masks_packed: getMasks(0) of the current state as packed words -- the
+ * bits mrts_get_masks writes, the source channel included; parked games' rows are
+ * zero.  A launch of its own that reads the games only: the bound dense mask
+ * outputs, and what delta masks know about them, stay as they are.  MRTS_EINVAL for
+ * a null handle or output, MRTS_ESTATE while no workspace is bound. */
+int mrts_get_masks_packed(mrts_vec *h, void *stream, int32_t *packed);
+
+/* Dense -> packed: channel bit = (mask != 0), source bit = (source != 0).  Every row is
+ * read and kept, a non-source row's stray bits too: the conversion is lossless. */
+int mrts_pack_masks(void *stream, const int32_t *mask, const int32_t *source, int32_t num_envs, int32_t hw, int32_t *packed);
+
+/* Packed -> dense: writes every element of mask [num_envs][hw][78] and source
+ * [num_envs][hw] as 0 or 1 (16-byte stores when `mask` is 16-byte aligned). */
+int mrts_unpack_masks(void *stream, const int32_t *packed, int32_t num_envs, int32_t hw, int32_t *mask, int32_t *source);
+
+/* mrts_policy_sample, mrts_policy_evaluate and mrts_policy_evaluate_backward over
+ * packed masks: `packed` [num_envs][hw][3] stands for `mask, source`, and everything
+ * else -- contract, checks, stream rules -- is the dense call's, word for word.  The
+ * outputs are the dense calls' bit for bit: the arithmetic is the same code, only the
+ * way a row's 78 bits reach it differs. */
+int mrts_policy_sample_packed(void *stream, const float *logits, const int32_t *packed, int32_t num_envs, int32_t hw, int32_t env0,
+                              uint64_t seed, uint32_t step, int64_t *actions, float *logprob, float *entropy);
+int mrts_policy_evaluate_packed(void *stream, const float *logits, const int32_t *packed, int32_t num_envs, int32_t hw,
+                                const int64_t *actions, float *logprob, float *entropy);
+int mrts_policy_evaluate_backward_packed(void *stream, const float *logits, const int32_t *packed, int32_t num_envs, int32_t hw,
+                                         const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
+                                         float *grad_logits);
+
 /* Per-game rollout statistics, host int32 out[num_games][MRTS_GAME_STATS]:
  * game time (ticks since the game's last reset; the reference's gs.getTime()),
  * env steps of the episode, steps since creation, and three never-reset

@@ -3,7 +3,8 @@
 // One row per (env, cell): the reference's action_plane_space.nvec (vec_env.py:234),
 // seven components.  get_action_mask's 78 channels are the components' entries laid
 // end to end (component k owns channels ACT_OFF[k] .. ACT_OFF[k] + ACT_LEN[k] - 1);
-// getMasks' 79-bit word puts the source bit in front (channel ch = bit ch + 1).
+// getMasks' 79-bit word puts the source bit in front (channel ch = bit ch + 1); the same
+// word is the packed mask format (below).
 // Users: decode_row (mrts_engine.hip), cell_mask (mrts_rules.h), the stand-in samplers
 // (mrts_sampler.hip), the masked action head (mrts_policy.hip).  The oracle keeps
 // tables of its own: it is the independent reference.
@@ -61,6 +62,19 @@ __host__ __device__ inline int comp_of(int ch) {
 __host__ __device__ inline uint64_t comp_bits(uint64_t lo, uint64_t hi, int off, int len) {
     return ((lo >> off) | (off ? (hi << (64 - off)) : 0ull)) & ((1ull << len) - 1ull);
 }
+// Packed masks: getMasks' 79-bit word of a row as it is, three uint32 bit patterns per
+// row, packed [N][HW][MASK_PACKED_WORDS] int32 (include/microrts_amd.h states the same):
+//   word j, bit b = bit 32 j + b of the 79-bit word; bit 0 = the source channel,
+//   bit ch + 1 = mask channel ch; bits 79..95 are zero in everything the library writes
+//   and ignored by everything that reads.  A row is 12 bytes: 4-byte alignment only.
+constexpr int MASK_PACKED_WORDS = 3;
+static_assert(MRTS_MASK_BITS > 64 && MRTS_MASK_BITS <= 32 * MASK_PACKED_WORDS, "a row's bits fill the third word partly");
+constexpr uint32_t MASK_PACKED_W2 = (1u << (MRTS_MASK_BITS - 64)) - 1u;   // the third word's bits that belong to the row
+// a packed row's channels as comp_bits takes them: lo = channels 0..63, hi = channels 64..77 (bits 79..95 dropped)
+__host__ __device__ inline uint64_t packed_lo(uint32_t w0, uint32_t w1, uint32_t w2) {
+    return (uint64_t)(w0 >> 1) | ((uint64_t)w1 << 31) | ((uint64_t)(w2 & 1u) << 63);
+}
+__host__ __device__ inline uint64_t packed_hi(uint32_t w2) { return (uint64_t)((w2 & MASK_PACKED_W2) >> 1); }
 // A uniform pick among n entries from one random word.  With n = the component's length it
 // is the no-valid-entry draw: what every sampler writes for a component the mask leaves empty.
 __host__ __device__ inline int draw_uniform(uint32_t r, int n) { return (int)(((uint64_t)r * (uint32_t)n) >> 32); }

@@ -199,8 +199,10 @@ struct mrts_vec {
     //                            for parked ones), the others are untouched; a parked game's
     //                            k_step returns before any write and its rows stay zero
     //   mrts_add_map, mrts_set_reward_weight, mrts_set_bot_fusion, mrts_set_mask_delta, mrts_save_state,
-    //   mrts_get_raw_obs, mrts_render, mrts_game_stats, mrts_error_flags
-    //                            no effect (neither the state nor the buffer changes)
+    //   mrts_get_raw_obs, mrts_get_masks_packed, mrts_render, mrts_game_stats, mrts_error_flags
+    //                            no effect (neither the state nor the buffer changes; a caller who
+    //                            passes the bound mask buffer as the packed output has written into
+    //                            it and binds again, as after any write of its own)
     // and any of the launches above that fails while masks are bound clears it.
     int mask_delta = 1;          // requested
     bool masks_synced = false;
@@ -468,6 +470,15 @@ int mrts_get_masks(mrts_vec *h, void *stream, int32_t *mask, int32_t *source) {
     if (mask == h->next_mask && source == h->next_src) masks_written(h, e, true);
     else if (mask == h->next_mask || source == h->next_src) h->masks_synced = false;   // half the binding: not the engine's rows
     return e ? hip_fail(h, e, "masks launch") : MRTS_OK;
+}
+
+// A launch of its own into the caller's buffer: it reads the games, writes nothing the
+// engine owns and leaves the bound dense buffers and masks_synced as they are.
+int mrts_get_masks_packed(mrts_vec *h, void *stream, int32_t *packed) {
+    if (!h || !packed) return fail(h, MRTS_EINVAL, "get_masks_packed: null handle or output");
+    if (!bound(h)) return fail(h, MRTS_ESTATE, "get_masks_packed: workspace not bound");
+    hipError_t e = mrts_engine_masks_packed(&h->base, (hipStream_t)stream, packed);
+    return e ? hip_fail(h, e, "packed masks launch") : MRTS_OK;
 }
 
 // the step's parameters of one engine (mrts_step / mrts_step_weighted / mrts_step_group)
@@ -795,6 +806,38 @@ int mrts_policy_evaluate_backward(void *stream, const float *logits, const int32
         return MRTS_EINVAL;
     return mrts_engine_policy_eval_bwd(logits, mask, source, n, hw, actions, grad_logprob, grad_entropy, grad_logits,
                                        (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
+int mrts_pack_masks(void *stream, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw, int32_t *packed) {
+    if (!mask || !source || !packed || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
+    return mrts_engine_pack_masks(mask, source, (long long)n * hw, packed, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
+int mrts_unpack_masks(void *stream, const int32_t *packed, int32_t n, int32_t hw, int32_t *mask, int32_t *source) {
+    if (!packed || !mask || !source || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
+    return mrts_engine_unpack_masks(packed, (long long)n * hw, mask, source, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
+int mrts_policy_sample_packed(void *stream, const float *logits, const int32_t *packed, int32_t n, int32_t hw, int32_t env0,
+                              uint64_t seed, uint32_t step, int64_t *actions, float *logprob, float *entropy) {
+    if (!logits || !packed || !actions || !logprob || !entropy || env0 < 0 || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
+    return mrts_engine_policy_sample_packed(logits, packed, n, hw, env0, seed, step, actions, logprob, entropy, (hipStream_t)stream)
+               ? MRTS_EHIP : MRTS_OK;
+}
+
+int mrts_policy_evaluate_packed(void *stream, const float *logits, const int32_t *packed, int32_t n, int32_t hw,
+                                const int64_t *actions, float *logprob, float *entropy) {
+    if (!logits || !packed || !actions || !logprob || !entropy || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
+    return mrts_engine_policy_eval_packed(logits, packed, n, hw, actions, logprob, entropy, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
+int mrts_policy_evaluate_backward_packed(void *stream, const float *logits, const int32_t *packed, int32_t n, int32_t hw,
+                                         const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
+                                         float *grad_logits) {
+    if (!logits || !packed || !actions || !grad_logprob || !grad_entropy || !grad_logits || !sampler_rows_ok(n, hw))
+        return MRTS_EINVAL;
+    return mrts_engine_policy_eval_bwd_packed(logits, packed, n, hw, actions, grad_logprob, grad_entropy, grad_logits,
+                                              (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
 int mrts_bind_mask_outputs(mrts_vec *h, int32_t *mask, int32_t *source) {

@@ -116,7 +116,17 @@ hipError_t mrts_engine_policy_eval(const float *logits, const int32_t *mask, con
                                    float *logprob, float *entropy, hipStream_t s);
 hipError_t mrts_engine_policy_eval_bwd(const float *logits, const int32_t *mask, const int32_t *src, int n, int hw, const int64_t *act,
                                        const float *g_lp, const float *g_ent, float *grad, hipStream_t s);
+// the same three over packed masks [n][hw][3] (mrts_actions.h), and the converters (rows = n * hw)
+hipError_t mrts_engine_policy_sample_packed(const float *logits, const int32_t *packed, int n, int hw, int env0, uint64_t seed,
+                                            uint32_t step, int64_t *act, float *logprob, float *entropy, hipStream_t s);
+hipError_t mrts_engine_policy_eval_packed(const float *logits, const int32_t *packed, int n, int hw, const int64_t *act, float *logprob,
+                                          float *entropy, hipStream_t s);
+hipError_t mrts_engine_policy_eval_bwd_packed(const float *logits, const int32_t *packed, int n, int hw, const int64_t *act,
+                                              const float *g_lp, const float *g_ent, float *grad, hipStream_t s);
+hipError_t mrts_engine_pack_masks(const int32_t *mask, const int32_t *src, long long rows, int32_t *packed, hipStream_t s);
+hipError_t mrts_engine_unpack_masks(const int32_t *packed, long long rows, int32_t *mask, int32_t *src, hipStream_t s);
 // mrts_engine.hip again (mrts_engine_bot_lds_bytes: mrts_bots.hip)
+hipError_t mrts_engine_masks_packed(const EngineParams *p, hipStream_t s, int32_t *packed);
 hipError_t mrts_engine_render(const EngineParams *p, hipStream_t s, int game, int map, int size, uint8_t *rgb);
 size_t mrts_engine_lds_bytes(int HW, int W);
 size_t mrts_engine_bot_lds_bytes(int HW, int W);

@@ -19,7 +19,7 @@
 // (delta masks, stream_masks_delta).
 // A step launch takes a StepGroup: one or more engines (map-size buckets) cut
 // into grid segments, bot games first (mrts_step_group).
-// In this unit: the game step, the output streams (reset / masks / outputs / raw obs),
+// In this unit: the game step, the output streams (reset / masks / packed masks / outputs / raw obs),
 // the renderer, their launchers.  Elsewhere: the scripted opponents (mrts_bots.hip), the
 // stand-in samplers (mrts_sampler.hip), the masked action head (mrts_policy.hip).
 //
@@ -702,6 +702,55 @@ __global__ __launch_bounds__(NT) void k_masks(EngineParams p) {
     }
     load_game<NT>(p, L, g);
     emit_outputs<NT, 29, int32_t>(p, L, game_of(p, g), false, true, L.sc[SC_RES0], L.sc[SC_RES1]);
+}
+
+// ---------------------------------------------------------------------------
+// Packed mask kernel: getMasks(0)'s 79-bit words as they are -> packed [N][HW][3]
+// (mrts_actions.h), the dense buffers and EngineParams::mask / src_out untouched.
+// cell_mask's words go to LDS in output order (a game's views are adjacent envs: one
+// contiguous run of nviews * HW * 3 words, staged at L.outw -- 16-byte aligned, 24 of
+// the region's 32 bytes per cell) and leave with 16-byte stores when the game's first
+// row is 16-byte aligned (12-byte rows: an odd HW leaves some envs unaligned), per word
+// otherwise.  A parked game's rows are zero.
+template <int NT>
+__global__ __launch_bounds__(NT) void k_masks_packed(EngineParams p, int32_t* __restrict__ packed) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    Lds L = carve(smem, p.HW, p.W, NT);
+    const int g = blockIdx.x, HW = p.HW;
+    const Game G = game_of(p, g);
+    int32_t* out = packed + (size_t)G.env0 * HW * MASK_PACKED_WORDS;
+    const int nw = G.nviews * HW * MASK_PACKED_WORDS;
+    const bool al16 = ((uintptr_t)out & 15u) == 0;
+    if (game_parked(p, g)) {
+        if (al16) {
+            for (int k = threadIdx.x; k < nw / 4; k += NT) st16(out + 4 * k, 0, 0, 0, 0);
+            for (int i = 4 * (nw / 4) + threadIdx.x; i < nw; i += NT) out[i] = 0;
+        } else {
+            for (int i = threadIdx.x; i < nw; i += NT) out[i] = 0;
+        }
+        return;
+    }
+    load_game<NT>(p, L, g);
+    const Grid gd{p.W, p.H, HW};
+    const int res0 = L.sc[SC_RES0], res1 = L.sc[SC_RES1];
+    uint32_t* mw = L.outw;
+    for (int c = threadIdx.x; c < HW; c += NT) {
+        for (int v = 0; v < G.nviews; v++) {
+            uint32_t m[3];
+            cell_mask(gd, c, v, L.unit, L.act, L.wall, v == 0 ? res0 : res1, m);
+            mw[MASK_PACKED_WORDS * (v * HW + c)] = m[0];
+            mw[MASK_PACKED_WORDS * (v * HW + c) + 1] = m[1];
+            mw[MASK_PACKED_WORDS * (v * HW + c) + 2] = m[2] & MASK_PACKED_W2;
+        }
+    }
+    __syncthreads();
+    if (al16) {
+        const v4i* m4 = reinterpret_cast<const v4i*>(mw);
+        for (int k = threadIdx.x; k < nw / 4; k += NT) *reinterpret_cast<v4i*>(out + 4 * k) = m4[k];
+        for (int i = 4 * (nw / 4) + threadIdx.x; i < nw; i += NT) out[i] = (int32_t)mw[i];
+    } else {
+        for (int i = threadIdx.x; i < nw; i += NT) out[i] = (int32_t)mw[i];
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -1740,6 +1789,13 @@ hipError_t mrts_engine_reset(const EngineParams* p, hipStream_t s, const int32_t
     return mrts::dispatch(*p, mrts::K_RESET, s, games, maps, count);
 }
 hipError_t mrts_engine_masks(const EngineParams* p, hipStream_t s) { return mrts::dispatch(*p, mrts::K_MASKS, s, nullptr, nullptr, 0); }
+hipError_t mrts_engine_masks_packed(const EngineParams* p, hipStream_t s, int32_t* packed) {
+    const size_t sh = mrts_engine_lds_bytes(p->HW, p->W);
+    mrts::with_nt(mrts::step_nt(p->HW, false), [&](auto nt) {
+        hipLaunchKernelGGL(mrts::k_masks_packed<decltype(nt)::value>, dim3(p->G), dim3(decltype(nt)::value), sh, s, *p, packed);
+    });
+    return hipGetLastError();
+}
 hipError_t mrts_engine_outputs(const EngineParams* p, hipStream_t s) { return mrts::dispatch(*p, mrts::K_OUTPUTS, s, nullptr, nullptr, 0); }
 hipError_t mrts_engine_raw_obs(const EngineParams* p, hipStream_t s, int32_t* raw) {
     const size_t sh = mrts_engine_lds_bytes(p->HW, p->W);

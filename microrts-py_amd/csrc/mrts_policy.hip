@@ -32,6 +32,14 @@
 // Per-env log-prob and entropy: lane k adds its component over the wave's rows in
 // float64 in row order, then a wave shuffle, then LDS across the waves, rounded once
 // to float32 -- no floating-point atomics, so two runs give the same bits.
+//
+// Packed masks (mrts_actions.h; k_policy_*_packed): the same bodies over the 79-bit
+// words.  Each lane loads its own row's three words, one coalesced 768-byte pass per
+// wave and group of 64 rows; the source ballot is bit 0; a source row's valid channels
+// are read out of the owner lane's registers, so per source row only the logits (and
+// the actions) are loaded and no load depends on another.  From the ballots on -- the
+// fold proper -- both forms run the same code: the results are the same bits.
+// In this unit too: the converters between the two forms (k_pack_masks, k_unpack_masks).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -60,34 +68,76 @@ struct WaveRow {
 };
 
 // a source row's words as loaded: channels lane and 64 + lane (lanes >= 14 re-read channel
-// 77 and ignore it), and lane k < 7's action of component k (EVAL / BWD)
+// 77 and ignore it), and lane k < 7's action of component k (EVAL / BWD).  Dense masks:
+// the two mask words beside the logits.  Packed masks (mrts_actions.h): no mask load at
+// all -- the row's words come out of the registers of the lane that owns the row.
+// (-DMRTS_PACKED_ROW_LOADS, A/B builds only: the wave keeps word 0 of its 64 rows and
+// loads a source row's three words beside its logits, as the dense form does.)
+template <bool PACKED>
 struct RowRegs {
     int m0, m1;
     float l0, l1;
     long long a;
 };
-template <Mode MODE>
-__device__ __forceinline__ void load_row(RowRegs& R, size_t row, const int32_t* __restrict__ mask, const float* __restrict__ logits,
-                                         const int64_t* __restrict__ act, int lane) {
-    const int32_t* m = mask + row * MRTS_MASK_CH;
-    const float* l = logits + row * MRTS_MASK_CH;
-    const int c1 = 64 + min(lane, MRTS_MASK_CH - 65);   // unconditional loads: the compiler counts them, the next row's stay in flight
-    R.m0 = m[lane];
-    R.l0 = l[lane];
-    R.m1 = m[c1];
-    R.l1 = l[c1];
+template <>
+struct RowRegs<true> {
+    uint32_t w0, w1, w2;   // the row's packed words, the same in every lane
+    float l0, l1;
+    long long a;
+};
+// a wave's 64 packed rows, one per lane (dense masks: unused)
+struct GroupWords {
+    uint32_t w0, w1, w2;
+};
+template <Mode MODE, bool PACKED>
+__device__ __forceinline__ void load_row(RowRegs<PACKED>& R, size_t row, int r, const GroupWords& gw, const int32_t* __restrict__ mask,
+                                         const float* __restrict__ logits, const int64_t* __restrict__ act, int lane) {
+    if constexpr (PACKED) {
+        const float* l = logits + row * MRTS_MASK_CH;
+        const int c1 = 64 + min(lane, MRTS_MASK_CH - 65);
+#ifdef MRTS_PACKED_ROW_LOADS
+        const int32_t* pr = mask + row * MASK_PACKED_WORDS;   // one address for the wave
+        R.w0 = (uint32_t)pr[0];
+        R.w1 = (uint32_t)pr[1];
+        R.w2 = (uint32_t)pr[2];
+#else
+        // r is wave-uniform: three readlanes, the row's words in scalar registers
+        R.w0 = (uint32_t)__builtin_amdgcn_readlane((int)gw.w0, r);
+        R.w1 = (uint32_t)__builtin_amdgcn_readlane((int)gw.w1, r);
+        R.w2 = (uint32_t)__builtin_amdgcn_readlane((int)gw.w2, r);
+#endif
+        R.l0 = l[lane];
+        R.l1 = l[c1];
+    } else {
+        const int32_t* m = mask + row * MRTS_MASK_CH;
+        const float* l = logits + row * MRTS_MASK_CH;
+        const int c1 = 64 + min(lane, MRTS_MASK_CH - 65);   // unconditional loads: the compiler counts them, the next row's stay in flight
+        R.m0 = m[lane];
+        R.l0 = l[lane];
+        R.m1 = m[c1];
+        R.l1 = l[c1];
+    }
     R.a = MODE == SAMPLE ? 0 : act[row * 7 + min(lane, 6)];
 }
 
 // Fold one source row (wave-uniform index r of the wave's 64 rows).  SAMPLE: the picks
 // go to s_out[r * 7 + k] over the no-valid-entry draw already there.  BWD: the valid
 // channels' gradient goes to g (the masked ones keep the +0.0f of the fill).
-template <Mode MODE>
-__device__ __forceinline__ void fold_row(const RowRegs& R, int r, int lane, WaveRow& W, const uint32_t (&r8)[8], int64_t* __restrict__ s_out,
+template <Mode MODE, bool PACKED>
+__device__ __forceinline__ void fold_row(const RowRegs<PACKED>& R, int r, int lane, WaveRow& W, const uint32_t (&r8)[8], int64_t* __restrict__ s_out,
                                          double& slp, double& sent, float g_lp, float g_ent, float* __restrict__ g) {
 #pragma clang fp contract(off)   // no fused multiply-adds: sample, evaluate and the backward round alike, bit for bit
     const bool hi = lane < MRTS_MASK_CH - 64;
-    const uint64_t vlo = __ballot(R.m0 != 0), vhi = __ballot(hi && R.m1 != 0);
+    uint64_t vlo, vhi;
+    if constexpr (PACKED) {
+        const uint32_t w0 = (uint32_t)__builtin_amdgcn_readfirstlane((int)R.w0), w1 = (uint32_t)__builtin_amdgcn_readfirstlane((int)R.w1),
+                       w2 = (uint32_t)__builtin_amdgcn_readfirstlane((int)R.w2);
+        vlo = packed_lo(w0, w1, w2);
+        vhi = packed_hi(w2);
+    } else {
+        vlo = __ballot(R.m0 != 0);
+        vhi = __ballot(hi && R.m1 != 0);
+    }
     W.l[lane] = R.l0;
     if (hi) W.l[64 + lane] = R.l1;
     if (MODE == SAMPLE && lane == r) {
@@ -158,26 +208,51 @@ __device__ __forceinline__ void fold_row(const RowRegs& R, int r, int lane, Wave
 
 // The source rows `pending` (bits of the wave's 64 rows from row0) in ascending order,
 // the next row's loads issued before the current one is folded.
-template <Mode MODE>
+template <Mode MODE, bool PACKED>
 __device__ __forceinline__ void fold_rows(uint64_t pending, size_t row0, int lane, const float* __restrict__ logits,
-                                          const int32_t* __restrict__ mask, const int64_t* __restrict__ act, WaveRow& W,
-                                          const uint32_t (&r8)[8], int64_t* __restrict__ s_out, double& slp, double& sent, float g_lp,
-                                          float g_ent, float* __restrict__ grad) {
+                                          const int32_t* __restrict__ mask, const GroupWords& gw, const int64_t* __restrict__ act,
+                                          WaveRow& W, const uint32_t (&r8)[8], int64_t* __restrict__ s_out, double& slp, double& sent,
+                                          float g_lp, float g_ent, float* __restrict__ grad) {
     if (!pending) return;
     int r = __builtin_ctzll(pending);
     pending &= pending - 1ull;
-    RowRegs cur;
-    load_row<MODE>(cur, row0 + r, mask, logits, act, lane);
+    RowRegs<PACKED> cur;
+    load_row<MODE, PACKED>(cur, row0 + r, r, gw, mask, logits, act, lane);
     while (true) {
         const bool more = pending != 0;
         const int rn = more ? __builtin_ctzll(pending) : r;   // none left: a harmless re-read
         pending &= pending - 1ull;
-        RowRegs nxt;
-        load_row<MODE>(nxt, row0 + rn, mask, logits, act, lane);
-        fold_row<MODE>(cur, r, lane, W, r8, s_out, slp, sent, g_lp, g_ent, MODE == BWD ? grad + (row0 + r) * MRTS_MASK_CH : nullptr);
+        RowRegs<PACKED> nxt;
+        load_row<MODE, PACKED>(nxt, row0 + rn, rn, gw, mask, logits, act, lane);
+        fold_row<MODE, PACKED>(cur, r, lane, W, r8, s_out, slp, sent, g_lp, g_ent,
+                               MODE == BWD ? grad + (row0 + r) * MRTS_MASK_CH : nullptr);
         if (!more) break;
         cur = nxt;
         r = rn;
+    }
+}
+
+// The source word of this lane's row among the wave's 64 rows from row0 (rb of them
+// exist; tail lanes re-read the last row: unconditional loads).  Packed masks: the row's
+// three words, each lane its own row in one coalesced 768-byte pass -- the source word
+// is bit 0, and the mask of every row the wave will fold is in registers from here on.
+template <bool PACKED>
+__device__ __forceinline__ int group_source(const int32_t* __restrict__ mask, const int32_t* __restrict__ src, size_t row0, int rb,
+                                            int lane, GroupWords& gw) {
+    const size_t row = row0 + min(lane, rb - 1);
+    if constexpr (PACKED) {
+        const int32_t* pr = mask + row * MASK_PACKED_WORDS;
+        gw.w0 = (uint32_t)pr[0];
+#ifdef MRTS_PACKED_ROW_LOADS
+        gw.w1 = gw.w2 = 0;
+#else
+        gw.w1 = (uint32_t)pr[1];
+        gw.w2 = (uint32_t)pr[2];
+#endif
+        return (int)(gw.w0 & 1u);
+    } else {
+        gw.w0 = gw.w1 = gw.w2 = 0;
+        return src[row];
     }
 }
 
@@ -212,10 +287,11 @@ __device__ __forceinline__ void reduce_env(double slp, double sent, float* __res
 // logprob [N] f32, entropy [N] f32.  A wave stages its 64 rows' actions in LDS and
 // writes them with 16-byte stores when the env's first row is 16-byte aligned (56-byte
 // rows: an odd hw with an odd env is not), per element otherwise.
-__global__ __launch_bounds__(PT) void k_policy_sample(const float* __restrict__ logits, const int32_t* __restrict__ mask,
-                                                      const int32_t* __restrict__ src, int hw, int env0, uint64_t seed, uint32_t step,
-                                                      int64_t* __restrict__ act, float* __restrict__ logprob,
-                                                      float* __restrict__ entropy) {
+// PACKED (the three bodies below): `mask` is packed [N][HW][3] and `src` is not read.
+template <bool PACKED>
+__device__ __forceinline__ void policy_sample(const float* __restrict__ logits, const int32_t* __restrict__ mask,
+                                              const int32_t* __restrict__ src, int hw, int env0, uint64_t seed, uint32_t step,
+                                              int64_t* __restrict__ act, float* __restrict__ logprob, float* __restrict__ entropy) {
     __shared__ __attribute__((aligned(16))) int64_t s_out[PW][64 * 7];
     __shared__ WaveRow s_row[PW];
     const int e = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -225,7 +301,8 @@ __global__ __launch_bounds__(PT) void k_policy_sample(const float* __restrict__ 
     for (int c0 = w * 64; c0 < hw; c0 += PT) {
         const int rb = min(64, hw - c0);
         const bool in = lane < rb;
-        const int s_raw = src[base + c0 + min(lane, rb - 1)];   // unconditional (tail lanes re-read the last row): the Philox words are drawn behind it
+        GroupWords gw;
+        const int s_raw = group_source<PACKED>(mask, src, base + c0, rb, lane, gw);   // unconditional: the Philox words are drawn behind it
         uint32_t r8[8];
         philox_row(env0 + e, c0 + lane, seed, step, r8);
         if (in) {
@@ -233,8 +310,8 @@ __global__ __launch_bounds__(PT) void k_policy_sample(const float* __restrict__ 
             for (int k = 0; k < ACT_COMPONENTS; k++) s_out[w][lane * 7 + k] = draw_uniform(r8[k], ACT_LEN[k]);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        fold_rows<SAMPLE>(__ballot(in && s_raw != 0), base + c0, lane, logits, mask, nullptr, s_row[w], r8, s_out[w], slp, sent, 0.0f, 0.0f,
-                          nullptr);
+        fold_rows<SAMPLE, PACKED>(__ballot(in && s_raw != 0), base + c0, lane, logits, mask, gw, nullptr, s_row[w], r8, s_out[w], slp, sent,
+                                  0.0f, 0.0f, nullptr);
         int64_t* ob = act + (base + c0) * 7;
         const int onel = rb * 7;
         if (al16) {
@@ -252,9 +329,10 @@ __global__ __launch_bounds__(PT) void k_policy_sample(const float* __restrict__ 
 }
 
 // The same inputs + the caller's actions -> logprob [N], entropy [N].
-__global__ __launch_bounds__(PT) void k_policy_eval(const float* __restrict__ logits, const int32_t* __restrict__ mask,
-                                                    const int32_t* __restrict__ src, int hw, const int64_t* __restrict__ act,
-                                                    float* __restrict__ logprob, float* __restrict__ entropy) {
+template <bool PACKED>
+__device__ __forceinline__ void policy_eval(const float* __restrict__ logits, const int32_t* __restrict__ mask,
+                                            const int32_t* __restrict__ src, int hw, const int64_t* __restrict__ act,
+                                            float* __restrict__ logprob, float* __restrict__ entropy) {
     __shared__ WaveRow s_row[PW];
     const int e = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const size_t base = (size_t)e * hw;
@@ -262,9 +340,10 @@ __global__ __launch_bounds__(PT) void k_policy_eval(const float* __restrict__ lo
     double slp = 0.0, sent = 0.0;
     for (int c0 = w * 64; c0 < hw; c0 += PT) {
         const int rb = min(64, hw - c0);
-        const int s_raw = src[base + c0 + min(lane, rb - 1)];
-        fold_rows<EVAL>(__ballot(lane < rb && s_raw != 0), base + c0, lane, logits, mask, act, s_row[w], r8, nullptr, slp, sent, 0.0f, 0.0f,
-                        nullptr);
+        GroupWords gw;
+        const int s_raw = group_source<PACKED>(mask, src, base + c0, rb, lane, gw);
+        fold_rows<EVAL, PACKED>(__ballot(lane < rb && s_raw != 0), base + c0, lane, logits, mask, gw, act, s_row[w], r8, nullptr, slp, sent,
+                                0.0f, 0.0f, nullptr);
     }
     reduce_env(slp, sent, logprob, entropy, e);
 }
@@ -273,10 +352,11 @@ __global__ __launch_bounds__(PT) void k_policy_eval(const float* __restrict__ lo
 // workgroup fills its env's rows with +0.0f (16-byte stores when the env's first row
 // is 16-byte aligned -- 312-byte rows: an odd hw with an odd env is not -- per element
 // otherwise), then the waves store the source rows' valid channels over the fill.
-__global__ __launch_bounds__(PT) void k_policy_eval_bwd(const float* __restrict__ logits, const int32_t* __restrict__ mask,
-                                                        const int32_t* __restrict__ src, int hw, const int64_t* __restrict__ act,
-                                                        const float* __restrict__ g_lp, const float* __restrict__ g_ent,
-                                                        float* __restrict__ grad) {
+template <bool PACKED>
+__device__ __forceinline__ void policy_eval_bwd(const float* __restrict__ logits, const int32_t* __restrict__ mask,
+                                                const int32_t* __restrict__ src, int hw, const int64_t* __restrict__ act,
+                                                const float* __restrict__ g_lp, const float* __restrict__ g_ent,
+                                                float* __restrict__ grad) {
     __shared__ WaveRow s_row[PW];
     const int e = blockIdx.x, w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const size_t base = (size_t)e * hw;
@@ -296,9 +376,122 @@ __global__ __launch_bounds__(PT) void k_policy_eval_bwd(const float* __restrict_
     double slp = 0.0, sent = 0.0;
     for (int c0 = w * 64; c0 < hw; c0 += PT) {
         const int rb = min(64, hw - c0);
-        const int s_raw = src[base + c0 + min(lane, rb - 1)];
-        fold_rows<BWD>(__ballot(lane < rb && s_raw != 0), base + c0, lane, logits, mask, act, s_row[w], r8, nullptr, slp, sent, glp, gent,
-                       grad);
+        GroupWords gw;
+        const int s_raw = group_source<PACKED>(mask, src, base + c0, rb, lane, gw);
+        fold_rows<BWD, PACKED>(__ballot(lane < rb && s_raw != 0), base + c0, lane, logits, mask, gw, act, s_row[w], r8, nullptr, slp, sent,
+                               glp, gent, grad);
+    }
+}
+
+// The six kernels: the bodies above over dense masks (mask + src) and over packed ones.
+__global__ __launch_bounds__(PT) void k_policy_sample(const float* __restrict__ logits, const int32_t* __restrict__ mask,
+                                                      const int32_t* __restrict__ src, int hw, int env0, uint64_t seed, uint32_t step,
+                                                      int64_t* __restrict__ act, float* __restrict__ logprob,
+                                                      float* __restrict__ entropy) {
+    policy_sample<false>(logits, mask, src, hw, env0, seed, step, act, logprob, entropy);
+}
+__global__ __launch_bounds__(PT) void k_policy_eval(const float* __restrict__ logits, const int32_t* __restrict__ mask,
+                                                    const int32_t* __restrict__ src, int hw, const int64_t* __restrict__ act,
+                                                    float* __restrict__ logprob, float* __restrict__ entropy) {
+    policy_eval<false>(logits, mask, src, hw, act, logprob, entropy);
+}
+__global__ __launch_bounds__(PT) void k_policy_eval_bwd(const float* __restrict__ logits, const int32_t* __restrict__ mask,
+                                                        const int32_t* __restrict__ src, int hw, const int64_t* __restrict__ act,
+                                                        const float* __restrict__ g_lp, const float* __restrict__ g_ent,
+                                                        float* __restrict__ grad) {
+    policy_eval_bwd<false>(logits, mask, src, hw, act, g_lp, g_ent, grad);
+}
+__global__ __launch_bounds__(PT) void k_policy_sample_packed(const float* __restrict__ logits, const int32_t* __restrict__ packed, int hw,
+                                                             int env0, uint64_t seed, uint32_t step, int64_t* __restrict__ act,
+                                                             float* __restrict__ logprob, float* __restrict__ entropy) {
+    policy_sample<true>(logits, packed, nullptr, hw, env0, seed, step, act, logprob, entropy);
+}
+__global__ __launch_bounds__(PT) void k_policy_eval_packed(const float* __restrict__ logits, const int32_t* __restrict__ packed, int hw,
+                                                           const int64_t* __restrict__ act, float* __restrict__ logprob,
+                                                           float* __restrict__ entropy) {
+    policy_eval<true>(logits, packed, nullptr, hw, act, logprob, entropy);
+}
+__global__ __launch_bounds__(PT) void k_policy_eval_bwd_packed(const float* __restrict__ logits, const int32_t* __restrict__ packed, int hw,
+                                                               const int64_t* __restrict__ act, const float* __restrict__ g_lp,
+                                                               const float* __restrict__ g_ent, float* __restrict__ grad) {
+    policy_eval_bwd<true>(logits, packed, nullptr, hw, act, g_lp, g_ent, grad);
+}
+
+// ---------------------------------------------------------------------------
+// Converters between the dense masks and the packed words (mrts_actions.h), over
+// rows = N * HW flat rows: neither looks at env boundaries.
+constexpr int CV_ROWS = 256;   // rows per workgroup: PW waves of 64 (pack), an even count (unpack's 16-byte chunks)
+static_assert(CV_ROWS == 64 * PW && CV_ROWS % 2 == 0, "a wave per 64 rows; row pairs are 156 elements = 39 16-byte chunks");
+
+// mask [rows][78] i32, src [rows] i32 -> packed [rows][3].  A wave takes 64 rows: per
+// row two coalesced loads and two ballots (the fold's own first step), the row's owner
+// lane keeps the words, then one coalesced pass of 12-byte rows.  Every row is read:
+// a non-source row's bits are kept.
+__global__ __launch_bounds__(PT) void k_pack_masks(const int32_t* __restrict__ mask, const int32_t* __restrict__ src, long long rows,
+                                                   int32_t* __restrict__ packed) {
+    const int lane = threadIdx.x & 63;
+    const long long row0 = (long long)blockIdx.x * CV_ROWS + (threadIdx.x >> 6) * 64;
+    if (row0 >= rows) return;   // wave-uniform
+    const int rb = (int)min(64ll, rows - row0);
+    const int c1 = 64 + min(lane, MRTS_MASK_CH - 65);
+    const bool hi = lane < MRTS_MASK_CH - 64;
+    const int s_raw = src[row0 + min(lane, rb - 1)];
+    uint64_t lo_own = 0, hi_own = 0;
+#pragma unroll 8
+    for (int r = 0; r < 64; r++) {   // tail rows re-read the last one: unconditional loads, several rows in flight
+        const int32_t* m = mask + (size_t)(row0 + min(r, rb - 1)) * MRTS_MASK_CH;
+        const uint64_t vlo = __ballot(m[lane] != 0), vhi = __ballot(hi && m[c1] != 0);
+        if (lane == r) {
+            lo_own = vlo;
+            hi_own = vhi;
+        }
+    }
+    if (lane < rb) {
+        int32_t* o = packed + (size_t)(row0 + lane) * MASK_PACKED_WORDS;
+        o[0] = (int32_t)((uint32_t)(lo_own << 1) | (s_raw != 0 ? 1u : 0u));
+        o[1] = (int32_t)(uint32_t)(lo_own >> 31);
+        o[2] = (int32_t)((uint32_t)(lo_own >> 63) | (uint32_t)(hi_own << 1));
+    }
+}
+
+// packed [rows][3] -> mask [rows][78] i32, src [rows] i32, every element 0 or 1.  A
+// workgroup stages its CV_ROWS rows' words in LDS and streams the mask rows with
+// 16-byte stores (stream_masks' bit arithmetic, mrts_engine.hip): elements 4k .. 4k + 3
+// are channels ch .. ch + 3 of row r = bits ch + 1 .. ch + 4 of its word; ch is even and
+// only ch = 76, on an even row, runs into the next row's channels 0, 1.  An odd row
+// count leaves the last row's channels 76, 77 to a per-element tail; a mask pointer
+// that is not 16-byte aligned takes the per-element path throughout.
+__global__ __launch_bounds__(PT) void k_unpack_masks(const int32_t* __restrict__ packed, long long rows, int32_t* __restrict__ mask,
+                                                     int32_t* __restrict__ src) {
+    static_assert(MRTS_MASK_CH == 78, "mask row layout");
+    __shared__ uint32_t s_w[MASK_PACKED_WORDS * CV_ROWS + 2];   // + the word pair read behind the last row (never used)
+    const long long row0 = (long long)blockIdx.x * CV_ROWS;
+    const int nr = (int)min((long long)CV_ROWS, rows - row0);
+    const uint32_t* pw = reinterpret_cast<const uint32_t*>(packed) + (size_t)row0 * MASK_PACKED_WORDS;
+    for (int i = threadIdx.x; i < MASK_PACKED_WORDS * CV_ROWS + 2; i += PT) s_w[i] = i < MASK_PACKED_WORDS * nr ? pw[i] : 0u;
+    __syncthreads();
+    for (int r = threadIdx.x; r < nr; r += PT) src[row0 + r] = (int32_t)(s_w[MASK_PACKED_WORDS * r] & 1u);
+    int32_t* out = mask + (size_t)row0 * MRTS_MASK_CH;   // CV_ROWS * 312 B per workgroup: aligned as `mask` is
+    const int total = nr * MRTS_MASK_CH;
+    if (((uintptr_t)mask & 15u) == 0) {
+        for (int k = threadIdx.x; k < total / 4; k += PT) {
+            const int r = 4 * k / MRTS_MASK_CH, ch = 4 * k - r * MRTS_MASK_CH, b0 = ch + 1;
+            const int wr = MASK_PACKED_WORDS * r + (b0 >> 5);
+            const uint32_t lo = s_w[wr], hi = s_w[wr + 1];
+            const uint32_t fun = (uint32_t)((((uint64_t)hi << 32) | lo) >> (b0 & 31));
+            const uint32_t bits = ch == 76 ? ((fun & 3u) | ((hi << 1) & 0xCu)) : fun;
+            v4i v = {(int)(bits & 1u), (int)((bits >> 1) & 1u), (int)((bits >> 2) & 1u), (int)((bits >> 3) & 1u)};
+            *reinterpret_cast<v4i*>(out + 4 * k) = v;
+        }
+        for (int e = 4 * (total / 4) + threadIdx.x; e < total; e += PT) {
+            const int r = e / MRTS_MASK_CH, b = e % MRTS_MASK_CH + 1;
+            out[e] = (int)((s_w[MASK_PACKED_WORDS * r + (b >> 5)] >> (b & 31)) & 1u);
+        }
+    } else {
+        for (int e = threadIdx.x; e < total; e += PT) {
+            const int r = e / MRTS_MASK_CH, b = e % MRTS_MASK_CH + 1;
+            out[e] = (int)((s_w[MASK_PACKED_WORDS * r + (b >> 5)] >> (b & 31)) & 1u);
+        }
     }
 }
 
@@ -326,6 +519,40 @@ hipError_t mrts_engine_policy_eval_bwd(const float* logits, const int32_t* mask,
     if (n == 0) return hipSuccess;
     hipLaunchKernelGGL(mrts::policy::k_policy_eval_bwd, dim3((unsigned)n), dim3(mrts::policy::PT), 0, s, logits, mask, src, hw, act, g_lp,
                        g_ent, grad);
+    return hipGetLastError();
+}
+hipError_t mrts_engine_policy_sample_packed(const float* logits, const int32_t* packed, int n, int hw, int env0, uint64_t seed,
+                                            uint32_t step, int64_t* act, float* logprob, float* entropy, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(mrts::policy::k_policy_sample_packed, dim3((unsigned)n), dim3(mrts::policy::PT), 0, s, logits, packed, hw, env0,
+                       seed, step, act, logprob, entropy);
+    return hipGetLastError();
+}
+hipError_t mrts_engine_policy_eval_packed(const float* logits, const int32_t* packed, int n, int hw, const int64_t* act, float* logprob,
+                                          float* entropy, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(mrts::policy::k_policy_eval_packed, dim3((unsigned)n), dim3(mrts::policy::PT), 0, s, logits, packed, hw, act,
+                       logprob, entropy);
+    return hipGetLastError();
+}
+hipError_t mrts_engine_policy_eval_bwd_packed(const float* logits, const int32_t* packed, int n, int hw, const int64_t* act,
+                                              const float* g_lp, const float* g_ent, float* grad, hipStream_t s) {
+    if (n == 0) return hipSuccess;
+    hipLaunchKernelGGL(mrts::policy::k_policy_eval_bwd_packed, dim3((unsigned)n), dim3(mrts::policy::PT), 0, s, logits, packed, hw, act,
+                       g_lp, g_ent, grad);
+    return hipGetLastError();
+}
+// rows = n * hw >= 1 (mrts_capi.cpp: within the samplers' row bound, so the grid is below 2^23)
+hipError_t mrts_engine_pack_masks(const int32_t* mask, const int32_t* src, long long rows, int32_t* packed, hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    const unsigned grid = (unsigned)((rows + mrts::policy::CV_ROWS - 1) / mrts::policy::CV_ROWS);
+    hipLaunchKernelGGL(mrts::policy::k_pack_masks, dim3(grid), dim3(mrts::policy::PT), 0, s, mask, src, rows, packed);
+    return hipGetLastError();
+}
+hipError_t mrts_engine_unpack_masks(const int32_t* packed, long long rows, int32_t* mask, int32_t* src, hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    const unsigned grid = (unsigned)((rows + mrts::policy::CV_ROWS - 1) / mrts::policy::CV_ROWS);
+    hipLaunchKernelGGL(mrts::policy::k_unpack_masks, dim3(grid), dim3(mrts::policy::PT), 0, s, packed, rows, mask, src);
     return hipGetLastError();
 }
 }

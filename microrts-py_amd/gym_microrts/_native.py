@@ -108,6 +108,13 @@ SIGNATURES = {
                                           ctypes.c_uint32, P, P, P]),
     "mrts_policy_evaluate": (ctypes.c_int, [P, P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P]),
     "mrts_policy_evaluate_backward": (ctypes.c_int, [P, P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P, P]),
+    "mrts_get_masks_packed": (ctypes.c_int, [P, P, P]),
+    "mrts_pack_masks": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, P]),
+    "mrts_unpack_masks": (ctypes.c_int, [P, P, ctypes.c_int32, ctypes.c_int32, P, P]),
+    "mrts_policy_sample_packed": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                                 ctypes.c_uint32, P, P, P]),
+    "mrts_policy_evaluate_packed": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P]),
+    "mrts_policy_evaluate_backward_packed": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P, P]),
     "mrts_game_stats": (ctypes.c_int, [P, P, P]),
     "mrts_bind_mask_outputs": (ctypes.c_int, [P, P, P]),
     "mrts_set_bot_fusion": (ctypes.c_int, [P, ctypes.c_int32]),

@@ -344,6 +344,7 @@ class MicroRTSGridModeVecEnv:
         self.source_unit_idxs = np.tile(np.arange(self.height * self.width), (self.num_envs, 1))
         self.source_unit_idxs = self.source_unit_idxs.reshape((self.source_unit_idxs.shape + (1,)))
         self._mask_fresh = False   # _mask / _src hold getMasks(0) of the current state
+        self._packed = None        # get_action_mask_packed()'s device buffer, allocated at its first call
         self._pool = None          # numpy contract: page-locked output arrays (HostArrayPool)
         self._act_stage = None     # host actions: page-locked int64 staging buffer
         self._act_copied = None    # event after the staging buffer's last H2D copy (reused only once it fired)
@@ -429,6 +430,25 @@ class MicroRTSGridModeVecEnv:
         mask = self._host("mask", self._mask)
         self._sync()
         return mask
+
+    def get_action_mask_packed(self):
+        """get_action_mask() and source_unit_mask of the current state as getMasks' own
+        79-bit words: (N, H*W, 3) int32 -- bit 0 the source channel, bit ch + 1 mask
+        channel ch (include/microrts_amd.h; gym_microrts.policy_head takes it as it is).
+        A device tensor on the tensor and hybrid contracts, a numpy array on the numpy
+        contract.  Launched on every call from the games themselves (12 bytes a row), so
+        it is never stale -- after reset, step, reset_games, park_games and set_state
+        alike -- and the dense mask buffers are neither read nor written.  The tensor is
+        this env's buffer: valid until the next call."""
+        if self._packed is None:
+            with torch.cuda.device(self.device):
+                self._packed = torch.zeros((self.num_envs, self.height * self.width, 3), dtype=torch.int32, device=self.device)
+        self._launch("get_masks_packed", _native.lib().mrts_get_masks_packed, self._h, self._stream(), self._packed.data_ptr())
+        if self.contract != "numpy":
+            return self._packed
+        packed = self._host("packed", self._packed)
+        self._sync()
+        return packed
 
     @property
     def source_unit_mask(self):
@@ -929,6 +949,10 @@ class MicroRTSMixedMapVecEnv:
     def get_action_mask(self):
         return [e.get_action_mask() for e in self.envs]
 
+    def get_action_mask_packed(self):
+        """MicroRTSGridModeVecEnv.get_action_mask_packed() per bucket."""
+        return [e.get_action_mask_packed() for e in self.envs]
+
     def step_async(self, actions):
         assert len(actions) == len(self.envs)
         for e, a in zip(self.envs, actions):
@@ -1058,6 +1082,10 @@ class MicroRTSSizeCyclingVecEnv:
 
     def get_action_mask(self):
         return [e.get_action_mask() for e in self.envs]
+
+    def get_action_mask_packed(self):
+        """Per size engine, as get_action_mask(): rows of envs that play elsewhere are zero."""
+        return [e.get_action_mask_packed() for e in self.envs]
 
     def step_async(self, actions):
         assert len(actions) == len(self.envs)

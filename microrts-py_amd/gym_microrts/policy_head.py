@@ -13,6 +13,17 @@ tensor contract ([N, HW, 78] and [N, HW] int32 device tensors); `logits` is [N*H
 or [N, HW, 78] float32.  A component with no valid entry (every component of a
 non-source cell) contributes 0 to the log-prob and the entropy, as the reference's
 float32 arithmetic does.  There is no CPU path: a CPU tensor is an error.
+
+Packed masks: getMasks' 79-bit word per cell in three int32 words, [N, HW, 3] -- bit 0
+the source channel, bit ch + 1 mask channel ch (include/microrts_amd.h).  It is what
+`get_action_mask_packed()` returns and what a rollout buffer can afford to keep (12
+bytes a row against 316).  `sample` and `evaluate` take it in place of `mask` with no
+`source`, and give the dense calls' results bit for bit:
+
+    packed = policy_head.pack_masks(mask, source)          # or env.get_action_mask_packed()
+    mask, source = policy_head.unpack_masks(packed)
+    actions, logprob, entropy = policy_head.sample(logits, packed, seed=s, step=t)
+    logprob, entropy = policy_head.evaluate(logits, packed, actions=actions)
 """
 import ctypes
 
@@ -22,6 +33,7 @@ from . import _native
 
 CHANNELS = 78      # sum of the action plane's nvec (vec_env.py:234)
 COMPONENTS = 7
+PACKED_WORDS = 3   # a packed row: the source bit + 78 channels in 96 bits
 
 
 def _need(t, name, dtypes):
@@ -68,25 +80,111 @@ def _inputs(logits, mask, source, float_masks, actions=None):
     return logits.contiguous(), _as_int32(mask), _as_int32(source), n, hw
 
 
+def _is_packed(mask):
+    """A packed tensor by its shape: [N, HW, 3] (a dense mask ends in 78)."""
+    return isinstance(mask, torch.Tensor) and mask.dim() == 3 and mask.shape[2] == PACKED_WORDS
+
+
+def _format(mask, source):
+    """True for a packed call (packed masks, no source), False for a dense one (mask and
+    source); ValueError for the two mixed forms."""
+    if source is None:
+        if isinstance(mask, torch.Tensor) and mask.dim() >= 1 and mask.shape[-1] == CHANNELS:
+            raise ValueError(f"a dense mask [N, HW, {CHANNELS}] needs its source [N, HW]; only packed masks "
+                             f"[N, HW, {PACKED_WORDS}] come without one")
+        return True
+    if _is_packed(mask):
+        raise ValueError(f"packed masks [N, HW, {PACKED_WORDS}] hold the source channel (bit 0): pass source=None")
+    return False
+
+
+def _packed(packed):
+    """Check a packed tensor's type and shape; returns (N, HW)."""
+    _need(packed, "packed", (torch.int32,))
+    if packed.dim() != 3 or packed.shape[2] != PACKED_WORDS or packed.shape[1] < 1:
+        raise ValueError(f"packed must be [N, HW, {PACKED_WORDS}], not {tuple(packed.shape)}")
+    return int(packed.shape[0]), int(packed.shape[1])
+
+
+def _inputs_packed(logits, packed, actions=None):
+    """_inputs for a packed call; returns (logits, packed, N, HW) contiguous."""
+    _need(logits, "logits", (torch.float32,))
+    n, hw = _packed(packed)
+    if tuple(logits.shape) not in ((n * hw, CHANNELS), (n, hw, CHANNELS)):
+        raise ValueError(f"logits must be [N*HW, {CHANNELS}] or [N, HW, {CHANNELS}] with N, HW = {(n, hw)}, not {tuple(logits.shape)}")
+    if actions is not None:
+        _need(actions, "actions", (torch.int64,))
+        if actions.numel() != n * hw * COMPONENTS:
+            raise ValueError(f"actions must hold N*HW*{COMPONENTS} = {n * hw * COMPONENTS} elements, not {tuple(actions.shape)}")
+        _on_gpu(logits, logits=logits, packed=packed, actions=actions)
+    else:
+        _on_gpu(logits, logits=logits, packed=packed)
+    return logits.contiguous(), packed.contiguous(), n, hw
+
+
 def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
 
 
-def sample(logits, mask, source, *, seed, step, env0=0):
+def pack_masks(mask, source):
+    """Dense -> packed: `mask` [N, HW, 78] and `source` [N, HW] int32 device tensors ->
+    [N, HW, 3] int32.  A bit is set where the element is non-zero; every row is kept, a
+    non-source row's stray bits too."""
+    _need(mask, "mask", (torch.int32,))
+    _need(source, "source", (torch.int32,))
+    if mask.dim() != 3 or mask.shape[2] != CHANNELS or mask.shape[1] < 1:
+        raise ValueError(f"mask must be [N, HW, {CHANNELS}], not {tuple(mask.shape)}")
+    n, hw = int(mask.shape[0]), int(mask.shape[1])
+    if tuple(source.shape) != (n, hw):
+        raise ValueError(f"source must be [N, HW] = {(n, hw)}, not {tuple(source.shape)}")
+    _on_gpu(mask, mask=mask, source=source)
+    dev = mask.device
+    m, s = mask.contiguous(), source.contiguous()
+    packed = torch.empty((n, hw, PACKED_WORDS), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _native.lib().mrts_pack_masks(_stream(dev), m.data_ptr(), s.data_ptr(), n, hw, packed.data_ptr())
+    _native.check(rc, None, "pack_masks")
+    return packed
+
+
+def unpack_masks(packed):
+    """Packed [N, HW, 3] int32 -> (mask [N, HW, 78], source [N, HW]) int32 of 0 / 1, the
+    tensors `get_action_mask()` and `source_unit_mask` return on the tensor contract."""
+    n, hw = _packed(packed)
+    _on_gpu(packed, packed=packed)
+    dev = packed.device
+    p = packed.contiguous()
+    mask = torch.empty((n, hw, CHANNELS), dtype=torch.int32, device=dev)
+    source = torch.empty((n, hw), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = _native.lib().mrts_unpack_masks(_stream(dev), p.data_ptr(), n, hw, mask.data_ptr(), source.data_ptr())
+    _native.check(rc, None, "unpack_masks")
+    return mask, source
+
+
+def sample(logits, mask, source=None, *, seed, step, env0=0):
     """Draw one action per component and cell: (actions [N, HW, 7] int64, what
     `step()` takes zero-copy; logprob [N]; entropy [N], float32).  The draw is the
     inverse CDF of the masked softmax at the Philox words keyed by (cell, env0 + env,
     step) under `seed` -- the stream of the engine's stand-in sampler, so a shard
-    [env0, env0 + N) draws exactly its slice of one larger batch.  No grad."""
-    lg, m, s, n, hw = _inputs(logits, mask, source, False)
+    [env0, env0 + N) draws exactly its slice of one larger batch.  No grad.
+    `mask` with `source`: the dense tensors; `mask` alone: packed [N, HW, 3] int32."""
+    packed = _format(mask, source)
+    if packed:
+        lg, m, n, hw = _inputs_packed(logits, mask)
+    else:
+        lg, m, s, n, hw = _inputs(logits, mask, source, False)
     dev = lg.device
     actions = torch.empty((n, hw, COMPONENTS), dtype=torch.int64, device=dev)
     logprob = torch.empty((n,), dtype=torch.float32, device=dev)
     entropy = torch.empty((n,), dtype=torch.float32, device=dev)
+    tail = (n, hw, int(env0), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(step) & 0xFFFFFFFF, actions.data_ptr(),
+            logprob.data_ptr(), entropy.data_ptr())
     with torch.cuda.device(dev):
-        rc = _native.lib().mrts_policy_sample(_stream(dev), lg.detach().data_ptr(), m.data_ptr(), s.data_ptr(), n, hw, int(env0),
-                                              ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(step) & 0xFFFFFFFF, actions.data_ptr(),
-                                              logprob.data_ptr(), entropy.data_ptr())
+        if packed:
+            rc = _native.lib().mrts_policy_sample_packed(_stream(dev), lg.detach().data_ptr(), m.data_ptr(), *tail)
+        else:
+            rc = _native.lib().mrts_policy_sample(_stream(dev), lg.detach().data_ptr(), m.data_ptr(), s.data_ptr(), *tail)
     _native.check(rc, None, "policy_sample")
     return actions, logprob, entropy
 
@@ -123,11 +221,52 @@ class _Evaluate(torch.autograd.Function):
         return grad, None, None, None, None, None
 
 
-def evaluate(logits, mask, source, actions):
+class _EvaluatePacked(torch.autograd.Function):
+    """_Evaluate over packed masks: saves the packed tensor, calls the packed backward."""
+
+    @staticmethod
+    def forward(ctx, logits, packed, actions, n, hw):
+        dev = logits.device
+        logprob = torch.empty((n,), dtype=torch.float32, device=dev)
+        entropy = torch.empty((n,), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            rc = _native.lib().mrts_policy_evaluate_packed(_stream(dev), logits.data_ptr(), packed.data_ptr(), n, hw,
+                                                           actions.data_ptr(), logprob.data_ptr(), entropy.data_ptr())
+        _native.check(rc, None, "policy_evaluate_packed")
+        ctx.save_for_backward(logits, packed, actions)
+        ctx.shape = (n, hw)
+        return logprob, entropy
+
+    @staticmethod
+    def backward(ctx, g_lp, g_ent):
+        logits, packed, actions = ctx.saved_tensors
+        n, hw = ctx.shape
+        dev = logits.device
+        zero = None
+        if g_lp is None or g_ent is None:
+            zero = torch.zeros((n,), dtype=torch.float32, device=dev)
+        g_lp = zero if g_lp is None else g_lp.to(torch.float32).contiguous()
+        g_ent = zero if g_ent is None else g_ent.to(torch.float32).contiguous()
+        grad = torch.empty_like(logits)   # the kernel writes every element
+        with torch.cuda.device(dev):
+            rc = _native.lib().mrts_policy_evaluate_backward_packed(_stream(dev), logits.data_ptr(), packed.data_ptr(), n, hw,
+                                                                    actions.data_ptr(), g_lp.data_ptr(), g_ent.data_ptr(),
+                                                                    grad.data_ptr())
+        _native.check(rc, None, "policy_evaluate_backward_packed")
+        return grad, None, None, None, None
+
+
+def evaluate(logits, mask, source=None, actions=None):
     """(logprob [N], entropy [N]) of `actions` ([N, HW, 7] or [N, HW*7] int64) under the
     masked softmax; differentiable in `logits` (the backward is a kernel too).  `mask` /
     `source` may also be the float32 copies a rollout buffer holds: they are converted
     to int32 once per call.  An action the mask forbids contributes -1e8, the
-    reference's float32 value."""
+    reference's float32 value.  `mask` alone (source=None, `actions` by keyword): packed
+    [N, HW, 3] int32, as it comes out of the rollout buffer."""
+    if actions is None:
+        raise TypeError("evaluate() needs the actions to evaluate")
+    if _format(mask, source):
+        lg, p, n, hw = _inputs_packed(logits, mask, actions)
+        return _EvaluatePacked.apply(lg, p, actions.contiguous(), n, hw)
     lg, m, s, n, hw = _inputs(logits, mask, source, True, actions)
     return _Evaluate.apply(lg, m, s, actions.contiguous(), n, hw)
