@@ -173,7 +173,8 @@ int mrts_step_weighted(mrts_vec *h, void *stream, const int64_t *actions, const 
 
 /* One step of several engines -- the map-size buckets of one mixed batch --
  * equivalent to mrts_step (io[i].reward == NULL) or mrts_step_weighted on each
- * hs[i] in order on `stream`.  Replaces the sequence of
+ * hs[i] in order on `stream`: mrts_step and mrts_step_weighted are this call
+ * with n = 1 and MRTS_GROUP_BOTS_FIRST.  Replaces the sequence of
  * JNIGridnetVecClient.gameStep calls that one reference vec env per map size
  * makes (vec_env.py:148-150: one size per env; vec_env.py:986-1003: gameStep),
  * so that engines whose kernels share planes, obs dtype and bot fusion run in

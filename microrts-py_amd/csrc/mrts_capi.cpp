@@ -190,7 +190,8 @@ struct mrts_vec {
     //                            into the buffer hands it back
     //   mrts_reset               set (k_reset writes every game's rows)
     //   mrts_step / _weighted / mrts_step_group
-    //                            dense step: set; delta step: stays set (it ran because it was set)
+    //                            all through step_engines: dense step: set; delta step: stays set (it
+    //                            ran because it was set); a failed bot or step launch: cleared
     //   mrts_get_masks           set when called with exactly the bound pointers (k_masks writes
     //                            every row); cleared when only one of the two is the bound one
     //   mrts_load_state          cleared once the state copy is queued, set by its outputs launch
@@ -226,6 +227,28 @@ static int fail(mrts_vec *h, int code, const std::string &msg) {
 }
 static int hip_fail(mrts_vec *h, hipError_t e, const char *what) {
     return fail(h, MRTS_EHIP, std::string(what) + ": " + hipGetErrorString(e));
+}
+
+// The templates of `count` maps into the workspace's slots first.. (walls, unit records, scalars),
+// staged here and drained before this returns.
+static hipError_t upload_maps(mrts_vec *h, hipStream_t s, const MapData *maps, int first, int count) {
+    const size_t HW = (size_t)h->HW;
+    std::vector<int4> mc(count * HW);
+    std::vector<uint8_t> mw(count * HW);
+    std::vector<int32_t> ms((size_t)count * MRTS_MAP_SCALARS, 0);
+    for (int i = 0; i < count; i++) {
+        std::memcpy(&mc[i * HW], maps[i].cells.data(), sizeof(int4) * HW);
+        std::memcpy(&mw[i * HW], maps[i].wall.data(), HW);
+        ms[i * MRTS_MAP_SCALARS + MRTS_M_RES0] = maps[i].res[0];
+        ms[i * MRTS_MAP_SCALARS + MRTS_M_RES1] = maps[i].res[1];
+        ms[i * MRTS_MAP_SCALARS + MRTS_M_NUNITS] = maps[i].nunits;
+    }
+    hipError_t e = hipMemcpyAsync(h->ws + h->off_mcells + first * HW * sizeof(int4), mc.data(), mc.size() * sizeof(int4), hipMemcpyHostToDevice, s);
+    if (!e) e = hipMemcpyAsync(h->ws + h->off_mwall + first * HW, mw.data(), mw.size(), hipMemcpyHostToDevice, s);
+    if (!e) e = hipMemcpyAsync(h->ws + h->off_mscal + (size_t)first * MRTS_MAP_SCALARS * sizeof(int32_t), ms.data(), ms.size() * sizeof(int32_t),
+                               hipMemcpyHostToDevice, s);
+    const hipError_t es = hipStreamSynchronize(s);   // a queued copy may still read the staging vectors after a later one failed
+    return e ? e : es;
 }
 
 extern "C" {
@@ -337,23 +360,10 @@ int mrts_bind_workspace(mrts_vec *h, void *dev, void *stream) {
     h->bots_ready = false;
     h->masks_synced = false;
     h->ws = (unsigned char *)dev;
-    const int nm = (int)h->maps.size();
-    std::vector<int4> mc((size_t)nm * h->HW);
-    std::vector<uint8_t> mw((size_t)nm * h->HW);
-    std::vector<int32_t> ms((size_t)nm * MRTS_MAP_SCALARS, 0);
-    for (int i = 0; i < nm; i++) {
-        std::memcpy(&mc[(size_t)i * h->HW], h->maps[i].cells.data(), sizeof(int4) * h->HW);
-        std::memcpy(&mw[(size_t)i * h->HW], h->maps[i].wall.data(), h->HW);
-        ms[i * MRTS_MAP_SCALARS + MRTS_M_RES0] = h->maps[i].res[0];
-        ms[i * MRTS_MAP_SCALARS + MRTS_M_RES1] = h->maps[i].res[1];
-        ms[i * MRTS_MAP_SCALARS + MRTS_M_NUNITS] = h->maps[i].nunits;
-    }
     std::vector<int32_t> genv((size_t)h->ngames * MRTS_GENV_WORDS, 0);
     for (int g = 0; g < h->ngames; g++) genv[(size_t)g * MRTS_GENV_WORDS + MRTS_G_MAP] = h->game_map[g];
     hipError_t e;
-    if ((e = hipMemcpyAsync(h->ws + h->off_mcells, mc.data(), mc.size() * sizeof(int4), hipMemcpyHostToDevice, s)) ||
-        (e = hipMemcpyAsync(h->ws + h->off_mwall, mw.data(), mw.size(), hipMemcpyHostToDevice, s)) ||
-        (e = hipMemcpyAsync(h->ws + h->off_mscal, ms.data(), ms.size() * sizeof(int32_t), hipMemcpyHostToDevice, s)) ||
+    if ((e = upload_maps(h, s, h->maps.data(), 0, (int)h->maps.size())) ||
         (e = hipMemcpyAsync(h->ws + h->off_genv, genv.data(), genv.size() * sizeof(int32_t), hipMemcpyHostToDevice, s)) ||
         (h->nbot && (e = hipMemcpyAsync(h->ws + h->off_botai, h->bot_ai.data(), h->nbot * sizeof(int32_t), hipMemcpyHostToDevice, s))) ||
         (h->nbot && (e = hipMemcpyAsync(h->ws + h->off_botai0, h->bot_ai0.data(), h->nbot * sizeof(int32_t), hipMemcpyHostToDevice, s))) ||
@@ -409,17 +419,6 @@ static bool fused(const mrts_vec *h) {
     return h->fuse && h->nbot_active > 0 && h->nbot0 == 0 && mrts_engine_fused_lds_bytes(h->HW, h->W, h->partial_obs) <= 163840;
 }
 
-// k_bot (when the tick's bot decisions are not already there) + k_step on s
-static hipError_t step_launch(mrts_vec *h, EngineParams &p, hipStream_t s) {
-    hipError_t e = hipSuccess;
-    if (!h->bots_ready) e = mrts_engine_bots(&p, s);
-    p.fuse_bots = fused(h) ? 1 : 0;
-    if (!e) e = mrts_engine_step(&p, s);
-    h->bots_ready = p.fuse_bots != 0;
-    masks_written(h, e, !p.mask_delta);
-    return e;
-}
-
 // after a reset of every game (games == null) or of the listed ones: with
 // fusion, decide their bot actions now (the next step will not launch k_bot)
 static hipError_t bots_after_reset(mrts_vec *h, hipStream_t s, const int32_t *games, int count) {
@@ -448,12 +447,18 @@ int mrts_set_mask_delta(mrts_vec *h, int32_t on) {
     return MRTS_OK;
 }
 
-int mrts_reset(mrts_vec *h, void *stream, void *obs) {
-    if (!bound(h) || !obs) return fail(h, MRTS_ESTATE, "reset: workspace not bound or obs null");
+// the parameters of a launch that writes obs and, when bound, the next tick's masks and sources
+static EngineParams out_params(const mrts_vec *h, void *obs) {
     EngineParams p = h->base;
     p.obs = obs;
     p.mask = h->next_mask;
     p.src_out = h->next_src;
+    return p;
+}
+
+int mrts_reset(mrts_vec *h, void *stream, void *obs) {
+    if (!bound(h) || !obs) return fail(h, MRTS_ESTATE, "reset: workspace not bound or obs null");
+    EngineParams p = out_params(h, obs);
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = mrts_engine_reset(&p, s, nullptr, nullptr, 0);
     masks_written(h, e, true);
@@ -483,10 +488,9 @@ int mrts_get_masks_packed(mrts_vec *h, void *stream, int32_t *packed) {
 
 // the step's parameters of one engine (mrts_step / mrts_step_weighted / mrts_step_group)
 static EngineParams step_params(const mrts_vec *h, const mrts_step_io &io) {
-    EngineParams p = h->base;
+    EngineParams p = out_params(h, io.obs);
     p.actions = io.actions;
     p.src = io.source;
-    p.obs = io.obs;
     p.raw_reward = io.raw_reward;
     p.done = io.done;
     if (io.reward) {
@@ -495,23 +499,12 @@ static EngineParams step_params(const mrts_vec *h, const mrts_step_io &io) {
         for (int k = 0; k < 6; k++) p.rw[k] = h->rw[k];
         p.shaping = h->shaping;
     }
-    p.mask = h->next_mask;
-    p.src_out = h->next_src;
     p.mask_delta = delta_ok(h) ? 1 : 0;
     return p;
 }
 
 static bool io_ok(const mrts_step_io &io, bool weighted) {
     return io.actions && io.source && io.obs && io.raw_reward && io.done && (!weighted || (io.reward && io.done0));
-}
-
-int mrts_step(mrts_vec *h, void *stream, const int64_t *actions, const int32_t *source, void *obs, double *raw_reward,
-              uint8_t *done) {
-    const mrts_step_io io{actions, source, obs, raw_reward, done, nullptr, nullptr};
-    if (!bound(h) || !io_ok(io, false)) return fail(h, MRTS_ESTATE, "step: workspace not bound or null buffer");
-    EngineParams p = step_params(h, io);
-    hipError_t e = step_launch(h, p, (hipStream_t)stream);
-    return e ? hip_fail(h, e, "step launch") : MRTS_OK;
 }
 
 int mrts_get_raw_obs(mrts_vec *h, void *stream, int32_t *raw) {
@@ -525,15 +518,6 @@ int mrts_set_reward_weight(mrts_vec *h, const double *w, int32_t shaping) {
     for (int k = 0; k < 6; k++) h->rw[k] = w[k];
     h->shaping = shaping ? 1 : 0;
     return MRTS_OK;
-}
-
-int mrts_step_weighted(mrts_vec *h, void *stream, const int64_t *actions, const int32_t *source, void *obs,
-                       double *raw_reward, uint8_t *done, double *reward, uint8_t *done0) {
-    const mrts_step_io io{actions, source, obs, raw_reward, done, reward, done0};
-    if (!bound(h) || !io_ok(io, true)) return fail(h, MRTS_ESTATE, "step_weighted: workspace not bound or null buffer");
-    EngineParams p = step_params(h, io);
-    hipError_t e = step_launch(h, p, (hipStream_t)stream);
-    return e ? hip_fail(h, e, "step launch") : MRTS_OK;
 }
 
 // A member may share a launch when its workgroup still leaves >= this many per CU
@@ -619,18 +603,20 @@ int mrts_step_group_plan(mrts_vec *const *hs, int32_t n, int32_t policy, int32_t
     return MRTS_OK;
 }
 
-int mrts_step_group(mrts_vec *const *hs, int32_t n, void *stream, const mrts_step_io *io, int32_t policy) {
-    int rc = group_check(hs, n, io, policy);
-    if (rc) return rc;
-    if (!io) return group_fail(hs, 0, MRTS_EINVAL, "step_group: null io");
-    hipStream_t s = (hipStream_t)stream;
+// The one step path: n engines under a group policy.  Per member: its parameters, k_bot when
+// the tick's bot decisions are not there yet, bot fusion; then the plan and, per launch, k_step
+// and what it means for the members' masks_synced and bots_ready.  A failed bot or step launch
+// while masks are bound clears that member's masks_synced.  `what` opens the error text.
+static int step_engines(mrts_vec *const *hs, int n, hipStream_t s, const mrts_step_io *io, int policy, const char *what) {
     EngineParams ps[MRTS_STEP_GROUP_MAX];
     for (int i = 0; i < n; i++) {
         mrts_vec *h = hs[i];
         ps[i] = step_params(h, io[i]);
-        // the tick's bot decisions, when an earlier launch did not make them
         hipError_t e = h->bots_ready ? hipSuccess : mrts_engine_bots(&ps[i], s);
-        if (e) return group_fail(hs, i, MRTS_EHIP, std::string("step_group bot launch: ") + hipGetErrorString(e));
+        if (e) {
+            masks_written(h, e, false);
+            return group_fail(hs, i, MRTS_EHIP, std::string(what) + " bot launch: " + hipGetErrorString(e));
+        }
         h->bots_ready = true;   // this tick's decisions are in botpa now, whatever happens below
         ps[i].fuse_bots = fused(h) ? 1 : 0;
     }
@@ -646,53 +632,77 @@ int mrts_step_group(mrts_vec *const *hs, int32_t n, void *stream, const mrts_ste
             }
         hipError_t e = mrts_engine_step_group(grp, m, s, (policy & MRTS_GROUP_BOTS_FIRST) != 0);
         // not atomic: members of launches 0..l-1 have stepped, those of l.. have not
-        // (include/microrts_amd.h); each member's bot state follows its own launch
+        // (include/microrts_amd.h); each member's mask and bot state follows its own launch
         for (int i = 0; i < n; i++)
-            if (launch_of[i] == l) masks_written(hs[i], e, !ps[i].mask_delta);
-        if (e) return group_fail(hs, first, MRTS_EHIP, std::string("step_group launch: ") + hipGetErrorString(e));
-        for (int i = 0; i < n; i++)
-            if (launch_of[i] == l) hs[i]->bots_ready = ps[i].fuse_bots != 0;
+            if (launch_of[i] == l) {
+                masks_written(hs[i], e, !ps[i].mask_delta);
+                hs[i]->bots_ready = ps[i].fuse_bots != 0;   // a fused step decided the next tick's
+            }
+        if (e) return group_fail(hs, first, MRTS_EHIP, std::string(what) + " launch: " + hipGetErrorString(e));
     }
     return MRTS_OK;
+}
+
+int mrts_step(mrts_vec *h, void *stream, const int64_t *actions, const int32_t *source, void *obs, double *raw_reward,
+              uint8_t *done) {
+    const mrts_step_io io{actions, source, obs, raw_reward, done, nullptr, nullptr};
+    if (!bound(h) || !io_ok(io, false)) return fail(h, MRTS_ESTATE, "step: workspace not bound or null buffer");
+    return step_engines(&h, 1, (hipStream_t)stream, &io, MRTS_GROUP_BOTS_FIRST, "step");
+}
+
+int mrts_step_weighted(mrts_vec *h, void *stream, const int64_t *actions, const int32_t *source, void *obs,
+                       double *raw_reward, uint8_t *done, double *reward, uint8_t *done0) {
+    const mrts_step_io io{actions, source, obs, raw_reward, done, reward, done0};
+    if (!bound(h) || !io_ok(io, true)) return fail(h, MRTS_ESTATE, "step_weighted: workspace not bound or null buffer");
+    return step_engines(&h, 1, (hipStream_t)stream, &io, MRTS_GROUP_BOTS_FIRST, "step");
+}
+
+int mrts_step_group(mrts_vec *const *hs, int32_t n, void *stream, const mrts_step_io *io, int32_t policy) {
+    int rc = group_check(hs, n, io, policy);
+    if (rc) return rc;
+    if (!io) return group_fail(hs, 0, MRTS_EINVAL, "step_group: null io");
+    return step_engines(hs, n, (hipStream_t)stream, io, policy, "step_group");
+}
+
+// mrts_reset_games (maps: each listed game's new map) / mrts_park_games (maps == null): the
+// whole list is validated before anything changes; then the host mirrors, the device's parked
+// flags when one changed, the list into scratch, k_reset over it (a parked game writes zero
+// obs / masks / sources) and a sync, for the host staging vector must outlive the copy.
+static int reset_listed(mrts_vec *h, hipStream_t s, const int32_t *games, const int32_t *maps, int count, void *obs,
+                        const std::string &what) {
+    if (count == 0) return MRTS_OK;
+    for (int i = 0; i < count; i++)
+        if (games[i] < 0 || games[i] >= h->ngames || (maps && (maps[i] < 0 || maps[i] >= (int)h->maps.size())))
+            return fail(h, MRTS_EINVAL, what + ": index out of range");
+    const uint8_t park = maps ? 0 : 1;
+    bool flags_changed = false;
+    for (int i = 0; i < count; i++) {
+        if (maps) h->game_map[games[i]] = maps[i];
+        flags_changed |= h->parked[games[i]] != park;
+        h->parked[games[i]] = park;
+    }
+    hipError_t e = flags_changed ? upload_parked(h, s) : hipSuccess;
+    if (e) return hip_fail(h, e, (what + " parked flags upload").c_str());
+    h->scratch_host.assign(games, games + count);
+    if (!maps) maps = games;   // (map list unused for parked games)
+    h->scratch_host.insert(h->scratch_host.end(), maps, maps + count);
+    int32_t *dg = (int32_t *)(h->ws + h->off_scratch);
+    e = hipMemcpyAsync(dg, h->scratch_host.data(), sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, s);
+    if (!e) {
+        EngineParams p = out_params(h, obs);
+        e = mrts_engine_reset(&p, s, dg, dg + count, count);
+    }
+    if (!e && !park) e = bots_after_reset(h, s, dg, count);
+    const hipError_t es = hipStreamSynchronize(s);
+    if (!e) e = es;
+    masks_written(h, e, false);   // the listed games' rows only
+    return e ? hip_fail(h, e, (what + " launch").c_str()) : MRTS_OK;
 }
 
 int mrts_reset_games(mrts_vec *h, void *stream, const int32_t *games, const int32_t *maps, int32_t count, void *obs) {
     if (!bound(h) || !obs || count < 0 || count > h->ngames || (count && (!games || !maps)))
         return fail(h, MRTS_EINVAL, "reset_games: bad arguments");
-    if (count == 0) return MRTS_OK;
-    for (int i = 0; i < count; i++) {
-        if (games[i] < 0 || games[i] >= h->ngames || maps[i] < 0 || maps[i] >= (int)h->maps.size())
-            return fail(h, MRTS_EINVAL, "reset_games: index out of range");
-        h->game_map[games[i]] = maps[i];
-    }
-    hipStream_t s = (hipStream_t)stream;
-    if (h->base.parked) {   // the listed games play again
-        bool any = false;
-        for (int i = 0; i < count; i++) {
-            any |= h->parked[games[i]] != 0;
-            h->parked[games[i]] = 0;
-        }
-        if (any) {
-            hipError_t e = upload_parked(h, s);
-            if (e) return hip_fail(h, e, "reset_games unpark");
-        }
-    }
-    h->scratch_host.assign(games, games + count);
-    h->scratch_host.insert(h->scratch_host.end(), maps, maps + count);
-    int32_t *dg = (int32_t *)(h->ws + h->off_scratch);
-    hipError_t e = hipMemcpyAsync(dg, h->scratch_host.data(), sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, s);
-    if (e) return hip_fail(h, e, "reset_games upload");
-    EngineParams p = h->base;
-    p.obs = obs;
-    p.mask = h->next_mask;
-    p.src_out = h->next_src;
-    e = mrts_engine_reset(&p, s, dg, dg + count, count);
-    masks_written(h, e, false);   // the listed games' rows only
-    if (!e) e = bots_after_reset(h, s, dg, count);
-    if (e) return hip_fail(h, e, "reset_games launch");
-    // the host staging vector must outlive the copy
-    e = hipStreamSynchronize(s);
-    return e ? hip_fail(h, e, "reset_games sync") : MRTS_OK;
+    return reset_listed(h, (hipStream_t)stream, games, maps, count, obs, "reset_games");
 }
 
 int mrts_add_map(mrts_vec *h, void *stream, const char *path, int32_t *index) {
@@ -709,20 +719,9 @@ int mrts_add_map(mrts_vec *h, void *stream, const char *path, int32_t *index) {
     if (m.w != h->W || m.h != h->H)
         return fail(h, MRTS_EINVAL, "add_map: all maps of one vec env must share height x width (vec_env.py:149-150)");
     const int i = (int)h->maps.size();
-    int32_t scal[MRTS_MAP_SCALARS] = {0};
-    scal[MRTS_M_RES0] = m.res[0];
-    scal[MRTS_M_RES1] = m.res[1];
-    scal[MRTS_M_NUNITS] = m.nunits;
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e;
     // a slot no game uses yet: nothing in flight reads it
-    if ((e = hipMemcpyAsync(h->ws + h->off_mcells + (size_t)i * h->HW * sizeof(int4), m.cells.data(), sizeof(int4) * h->HW,
-                            hipMemcpyHostToDevice, s)) ||
-        (e = hipMemcpyAsync(h->ws + h->off_mwall + (size_t)i * h->HW, m.wall.data(), h->HW, hipMemcpyHostToDevice, s)) ||
-        (e = hipMemcpyAsync(h->ws + h->off_mscal + (size_t)i * MRTS_MAP_SCALARS * sizeof(int32_t), scal, sizeof(scal),
-                            hipMemcpyHostToDevice, s)) ||
-        (e = hipStreamSynchronize(s)))
-        return hip_fail(h, e, "add_map upload");
+    hipError_t e = upload_maps(h, (hipStream_t)stream, &m, i, 1);
+    if (e) return hip_fail(h, e, "add_map upload");
     h->maps.push_back(std::move(m));
     h->map_path.emplace_back(path);
     h->base.nmaps = (int)h->maps.size();
@@ -733,28 +732,7 @@ int mrts_add_map(mrts_vec *h, void *stream, const char *path, int32_t *index) {
 int mrts_park_games(mrts_vec *h, void *stream, const int32_t *games, int32_t count, void *obs) {
     if (!bound(h) || !obs || count < 0 || count > h->ngames || (count && !games))
         return fail(h, MRTS_EINVAL, "park_games: bad arguments");
-    if (count == 0) return MRTS_OK;
-    for (int i = 0; i < count; i++) {
-        if (games[i] < 0 || games[i] >= h->ngames) return fail(h, MRTS_EINVAL, "park_games: game out of range");
-        h->parked[games[i]] = 1;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = upload_parked(h, s);
-    if (e) return hip_fail(h, e, "park_games upload");
-    // k_reset over the list: parked games write zero obs / masks / sources
-    h->scratch_host.assign(games, games + count);
-    h->scratch_host.insert(h->scratch_host.end(), games, games + count);   // (map list unused for parked games)
-    int32_t *dg = (int32_t *)(h->ws + h->off_scratch);
-    if ((e = hipMemcpyAsync(dg, h->scratch_host.data(), sizeof(int32_t) * 2 * count, hipMemcpyHostToDevice, s)))
-        return hip_fail(h, e, "park_games upload");
-    EngineParams p = h->base;
-    p.obs = obs;
-    p.mask = h->next_mask;
-    p.src_out = h->next_src;
-    e = mrts_engine_reset(&p, s, dg, dg + count, count);
-    if (!e) e = hipStreamSynchronize(s);
-    masks_written(h, e, false);   // the listed games' rows only (zeros)
-    return e ? hip_fail(h, e, "park_games launch") : MRTS_OK;
+    return reset_listed(h, (hipStream_t)stream, games, nullptr, count, obs, "park_games");
 }
 
 // The samplers' and the action head's shared shape check: the kernels index the n * hw rows
@@ -786,26 +764,54 @@ int mrts_sample_actions_src_group(void *stream, const mrts_sample_seg *segs, int
     return mrts_engine_sample_src_group(segs, nseg, seed, step, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
+// The action head's entry points, dense (mask + source) and packed (the words, no source),
+// over one check and one launcher each.
+static int policy_sample(int packed, void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n,
+                         int32_t hw, int32_t env0, uint64_t seed, uint32_t step, int64_t *actions, float *logprob, float *entropy) {
+    if (!logits || !mask || (!packed && !source) || !actions || !logprob || !entropy || env0 < 0 || !sampler_rows_ok(n, hw))
+        return MRTS_EINVAL;
+    return mrts_engine_policy_sample(packed, logits, mask, source, n, hw, env0, seed, step, actions, logprob, entropy,
+                                     (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+static int policy_evaluate(int packed, void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n,
+                           int32_t hw, const int64_t *actions, float *logprob, float *entropy) {
+    if (!logits || !mask || (!packed && !source) || !actions || !logprob || !entropy || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
+    return mrts_engine_policy_eval(packed, logits, mask, source, n, hw, actions, logprob, entropy, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+static int policy_evaluate_backward(int packed, void *stream, const float *logits, const int32_t *mask, const int32_t *source,
+                                    int32_t n, int32_t hw, const int64_t *actions, const float *grad_logprob,
+                                    const float *grad_entropy, float *grad_logits) {
+    if (!logits || !mask || (!packed && !source) || !actions || !grad_logprob || !grad_entropy || !grad_logits || !sampler_rows_ok(n, hw))
+        return MRTS_EINVAL;
+    return mrts_engine_policy_eval_bwd(packed, logits, mask, source, n, hw, actions, grad_logprob, grad_entropy, grad_logits,
+                                       (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
 int mrts_policy_sample(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw,
                        int32_t env0, uint64_t seed, uint32_t step, int64_t *actions, float *logprob, float *entropy) {
-    if (!logits || !mask || !source || !actions || !logprob || !entropy || env0 < 0 || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
-    return mrts_engine_policy_sample(logits, mask, source, n, hw, env0, seed, step, actions, logprob, entropy, (hipStream_t)stream)
-               ? MRTS_EHIP : MRTS_OK;
+    return policy_sample(0, stream, logits, mask, source, n, hw, env0, seed, step, actions, logprob, entropy);
 }
-
+int mrts_policy_sample_packed(void *stream, const float *logits, const int32_t *packed, int32_t n, int32_t hw, int32_t env0,
+                              uint64_t seed, uint32_t step, int64_t *actions, float *logprob, float *entropy) {
+    return policy_sample(1, stream, logits, packed, nullptr, n, hw, env0, seed, step, actions, logprob, entropy);
+}
 int mrts_policy_evaluate(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw,
                          const int64_t *actions, float *logprob, float *entropy) {
-    if (!logits || !mask || !source || !actions || !logprob || !entropy || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
-    return mrts_engine_policy_eval(logits, mask, source, n, hw, actions, logprob, entropy, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+    return policy_evaluate(0, stream, logits, mask, source, n, hw, actions, logprob, entropy);
 }
-
+int mrts_policy_evaluate_packed(void *stream, const float *logits, const int32_t *packed, int32_t n, int32_t hw,
+                                const int64_t *actions, float *logprob, float *entropy) {
+    return policy_evaluate(1, stream, logits, packed, nullptr, n, hw, actions, logprob, entropy);
+}
 int mrts_policy_evaluate_backward(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n,
                                   int32_t hw, const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
                                   float *grad_logits) {
-    if (!logits || !mask || !source || !actions || !grad_logprob || !grad_entropy || !grad_logits || !sampler_rows_ok(n, hw))
-        return MRTS_EINVAL;
-    return mrts_engine_policy_eval_bwd(logits, mask, source, n, hw, actions, grad_logprob, grad_entropy, grad_logits,
-                                       (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+    return policy_evaluate_backward(0, stream, logits, mask, source, n, hw, actions, grad_logprob, grad_entropy, grad_logits);
+}
+int mrts_policy_evaluate_backward_packed(void *stream, const float *logits, const int32_t *packed, int32_t n, int32_t hw,
+                                         const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
+                                         float *grad_logits) {
+    return policy_evaluate_backward(1, stream, logits, packed, nullptr, n, hw, actions, grad_logprob, grad_entropy, grad_logits);
 }
 
 int mrts_pack_masks(void *stream, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw, int32_t *packed) {
@@ -816,28 +822,6 @@ int mrts_pack_masks(void *stream, const int32_t *mask, const int32_t *source, in
 int mrts_unpack_masks(void *stream, const int32_t *packed, int32_t n, int32_t hw, int32_t *mask, int32_t *source) {
     if (!packed || !mask || !source || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
     return mrts_engine_unpack_masks(packed, (long long)n * hw, mask, source, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
-}
-
-int mrts_policy_sample_packed(void *stream, const float *logits, const int32_t *packed, int32_t n, int32_t hw, int32_t env0,
-                              uint64_t seed, uint32_t step, int64_t *actions, float *logprob, float *entropy) {
-    if (!logits || !packed || !actions || !logprob || !entropy || env0 < 0 || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
-    return mrts_engine_policy_sample_packed(logits, packed, n, hw, env0, seed, step, actions, logprob, entropy, (hipStream_t)stream)
-               ? MRTS_EHIP : MRTS_OK;
-}
-
-int mrts_policy_evaluate_packed(void *stream, const float *logits, const int32_t *packed, int32_t n, int32_t hw,
-                                const int64_t *actions, float *logprob, float *entropy) {
-    if (!logits || !packed || !actions || !logprob || !entropy || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
-    return mrts_engine_policy_eval_packed(logits, packed, n, hw, actions, logprob, entropy, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
-}
-
-int mrts_policy_evaluate_backward_packed(void *stream, const float *logits, const int32_t *packed, int32_t n, int32_t hw,
-                                         const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
-                                         float *grad_logits) {
-    if (!logits || !packed || !actions || !grad_logprob || !grad_entropy || !grad_logits || !sampler_rows_ok(n, hw))
-        return MRTS_EINVAL;
-    return mrts_engine_policy_eval_bwd_packed(logits, packed, n, hw, actions, grad_logprob, grad_entropy, grad_logits,
-                                              (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
 int mrts_bind_mask_outputs(mrts_vec *h, int32_t *mask, int32_t *source) {
@@ -959,22 +943,24 @@ int mrts_load_state(mrts_vec *h, void *stream, const void *src, void *obs) {
     std::memcpy(h->parked.data(), hdr.data() + sizeof sh + (size_t)h->ngames * sizeof(int32_t), (size_t)h->ngames);
     h->bots_ready = sh.bots_ready != 0;
     h->base.parked = sh.parked_any ? (uint8_t *)(h->ws + h->off_parked) : nullptr;
-    EngineParams p = h->base;
-    p.obs = obs;
-    p.mask = h->next_mask;
-    p.src_out = h->next_src;
+    EngineParams p = out_params(h, obs);
     e = mrts_engine_outputs(&p, s);
     masks_written(h, e, true);
     return e ? hip_fail(h, e, "load_state outputs launch") : MRTS_OK;
 }
 
+// every game's genv words, read back and drained
+static hipError_t read_genv(mrts_vec *h, void *stream, std::vector<int32_t> *genv) {
+    genv->resize((size_t)h->ngames * MRTS_GENV_WORDS);
+    hipStream_t s = (hipStream_t)stream;
+    hipError_t e = hipMemcpyAsync(genv->data(), h->ws + h->off_genv, genv->size() * sizeof(int32_t), hipMemcpyDeviceToHost, s);
+    return e ? e : hipStreamSynchronize(s);
+}
+
 int mrts_game_stats(mrts_vec *h, void *stream, int32_t *out) {
     if (!bound(h) || !out) return fail(h, MRTS_ESTATE, "game_stats: not bound or out null");
-    std::vector<int32_t> genv((size_t)h->ngames * MRTS_GENV_WORDS);
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(genv.data(), h->ws + h->off_genv, genv.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (!e) e = hipStreamSynchronize(s);
-    if (e) return hip_fail(h, e, "game_stats readback");
+    std::vector<int32_t> genv;
+    if (hipError_t e = read_genv(h, stream, &genv)) return hip_fail(h, e, "game_stats readback");
     static const int words[MRTS_GAME_STATS] = {MRTS_G_TIME, MRTS_G_STEPS, MRTS_G_TICKS, MRTS_G_SERIAL, MRTS_G_ORDERED, MRTS_G_EPISODES};
     for (int g = 0; g < h->ngames; g++)
         for (int k = 0; k < MRTS_GAME_STATS; k++) out[(size_t)g * MRTS_GAME_STATS + k] = genv[(size_t)g * MRTS_GENV_WORDS + words[k]];
@@ -983,11 +969,8 @@ int mrts_game_stats(mrts_vec *h, void *stream, int32_t *out) {
 
 int mrts_error_flags(mrts_vec *h, void *stream, int32_t *flags_out) {
     if (!bound(h) || !flags_out) return fail(h, MRTS_ESTATE, "error_flags: not bound");
-    std::vector<int32_t> genv((size_t)h->ngames * MRTS_GENV_WORDS);
-    hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(genv.data(), h->ws + h->off_genv, genv.size() * sizeof(int32_t), hipMemcpyDeviceToHost, s);
-    if (!e) e = hipStreamSynchronize(s);
-    if (e) return hip_fail(h, e, "error_flags readback");
+    std::vector<int32_t> genv;
+    if (hipError_t e = read_genv(h, stream, &genv)) return hip_fail(h, e, "error_flags readback");
     int32_t f = 0;
     for (int g = 0; g < h->ngames; g++) f |= genv[(size_t)g * MRTS_GENV_WORDS + MRTS_G_ERR];
     *flags_out = f;

@@ -98,7 +98,6 @@ extern "C" {
 hipError_t mrts_engine_reset(const EngineParams *p, hipStream_t s, const int32_t *games, const int32_t *maps, int count);
 hipError_t mrts_engine_masks(const EngineParams *p, hipStream_t s);
 hipError_t mrts_engine_outputs(const EngineParams *p, hipStream_t s);
-hipError_t mrts_engine_step(const EngineParams *p, hipStream_t s);
 hipError_t mrts_engine_step_group(const EngineParams *ps, int n, hipStream_t s, int bots_first);
 size_t mrts_engine_group_lds_bytes(int HW, int W, int fused, int NT, int partial);
 int mrts_engine_step_nt(int HW, int fused);
@@ -109,20 +108,16 @@ hipError_t mrts_engine_sample(const int32_t *mask, int n, int hw, int env0, uint
 hipError_t mrts_engine_sample_src(const int32_t *mask, const int32_t *src, int n, int hw, int env0, uint64_t seed, uint32_t step,
                                   int64_t *act, hipStream_t s);
 hipError_t mrts_engine_sample_src_group(const mrts_sample_seg *segs, int nseg, uint64_t seed, uint32_t step, hipStream_t s);
-// mrts_policy.hip: the masked action head (sample / evaluate / evaluate's backward)
-hipError_t mrts_engine_policy_sample(const float *logits, const int32_t *mask, const int32_t *src, int n, int hw, int env0,
-                                     uint64_t seed, uint32_t step, int64_t *act, float *logprob, float *entropy, hipStream_t s);
-hipError_t mrts_engine_policy_eval(const float *logits, const int32_t *mask, const int32_t *src, int n, int hw, const int64_t *act,
-                                   float *logprob, float *entropy, hipStream_t s);
-hipError_t mrts_engine_policy_eval_bwd(const float *logits, const int32_t *mask, const int32_t *src, int n, int hw, const int64_t *act,
-                                       const float *g_lp, const float *g_ent, float *grad, hipStream_t s);
-// the same three over packed masks [n][hw][3] (mrts_actions.h), and the converters (rows = n * hw)
-hipError_t mrts_engine_policy_sample_packed(const float *logits, const int32_t *packed, int n, int hw, int env0, uint64_t seed,
-                                            uint32_t step, int64_t *act, float *logprob, float *entropy, hipStream_t s);
-hipError_t mrts_engine_policy_eval_packed(const float *logits, const int32_t *packed, int n, int hw, const int64_t *act, float *logprob,
-                                          float *entropy, hipStream_t s);
-hipError_t mrts_engine_policy_eval_bwd_packed(const float *logits, const int32_t *packed, int n, int hw, const int64_t *act,
-                                              const float *g_lp, const float *g_ent, float *grad, hipStream_t s);
+// mrts_policy.hip: the masked action head (sample / evaluate / evaluate's backward).  packed == 0: `mask` is
+// the dense [n][hw][78] with its `src` [n][hw]; packed != 0: `mask` is the packed words [n][hw][3]
+// (mrts_actions.h) and `src` is not read.  Then the converters (rows = n * hw).
+hipError_t mrts_engine_policy_sample(int packed, const float *logits, const int32_t *mask, const int32_t *src, int n, int hw,
+                                     int env0, uint64_t seed, uint32_t step, int64_t *act, float *logprob, float *entropy,
+                                     hipStream_t s);
+hipError_t mrts_engine_policy_eval(int packed, const float *logits, const int32_t *mask, const int32_t *src, int n, int hw,
+                                   const int64_t *act, float *logprob, float *entropy, hipStream_t s);
+hipError_t mrts_engine_policy_eval_bwd(int packed, const float *logits, const int32_t *mask, const int32_t *src, int n, int hw,
+                                       const int64_t *act, const float *g_lp, const float *g_ent, float *grad, hipStream_t s);
 hipError_t mrts_engine_pack_masks(const int32_t *mask, const int32_t *src, long long rows, int32_t *packed, hipStream_t s);
 hipError_t mrts_engine_unpack_masks(const int32_t *packed, long long rows, int32_t *mask, int32_t *src, hipStream_t s);
 // mrts_engine.hip again (mrts_engine_bot_lds_bytes: mrts_bots.hip)

@@ -1638,8 +1638,6 @@ __global__ __launch_bounds__(256) void k_render(const int4* __restrict__ cells, 
 // ---------------------------------------------------------------------------
 // launchers
 
-enum Kind { K_RESET, K_MASKS, K_STEP, K_OUTPUTS };
-
 // Workgroup size of a map size: one lane per cell up to 256 lanes; the bot-fused
 // step needs a wave besides the bot's, so maps of <= 64 cells take 128 lanes there.
 __host__ __device__ inline int step_nt(int HW, bool fused) { return HW <= 64 && !fused ? 64 : HW <= 128 ? 128 : 256; }
@@ -1653,30 +1651,9 @@ static auto with_nt(int NT, F&& f) {
     return NT == 64 ? f(ic<64>{}) : NT == 128 ? f(ic<128>{}) : f(ic<256>{});
 }
 template <typename F>
-static void with_obs(bool partial, bool fl, F&& f) {
-    if (partial) fl ? f(ic<31>{}, float{}) : f(ic<31>{}, int32_t{});
-    else fl ? f(ic<29>{}, float{}) : f(ic<29>{}, int32_t{});
-}
-
-// One engine's step launch.  With both selfplay and bot games, the bot games take
-// the first workgroups: workgroups start in grid order, and a bot game's chain (the
-// fused bot after the tick) is the longest, so the short selfplay games fill the last
-// round (4096 selfplay + 4096 bot envs, 16x16: step 215 -> 196 us,
-// profiles/r03_ab/ab20_single_engine_bots_first/).
-static StepGroup one_engine(const EngineParams& p) {
-    StepGroup sg{};
-    sg.e[0] = p;
-    if (p.nsp_games > 0 && p.nsp_games < p.G) {
-        sg.seg_game[0] = p.nsp_games;
-        sg.seg_block[1] = p.G - p.nsp_games;
-        sg.seg_game[1] = 0;
-        sg.seg_block[2] = p.G;
-        sg.nseg = 2;
-    } else {
-        sg.seg_block[1] = p.G;
-        sg.nseg = 1;
-    }
-    return sg;
+static auto with_obs(bool partial, bool fl, F&& f) {
+    if (partial) return fl ? f(ic<31>{}, float{}) : f(ic<31>{}, int32_t{});
+    return fl ? f(ic<29>{}, float{}) : f(ic<29>{}, int32_t{});
 }
 
 // The step kernel of a launch's (planes, obs type, bot fusion).  No 64-lane launch
@@ -1692,38 +1669,25 @@ static void launch_step(const StepGroup& sg, int grid, size_t sh, hipStream_t s,
     });
 }
 
-static hipError_t dispatch(const EngineParams& p, Kind kind, hipStream_t s, const int32_t* games, const int32_t* maps, int count) {
-    return with_nt(step_nt(p.HW, kind == K_STEP && p.fuse_bots), [&](auto nt) -> hipError_t {
-        constexpr int NT = decltype(nt)::value;
-        size_t sh = lds_bytes(p.HW, p.W, NT);
-        int grid = p.G;
-        if (kind == K_RESET) {
-            grid = games ? count : p.G;
-            if (grid == 0) return hipSuccess;
-            with_obs(p.partial_obs, p.obs_float, [&](auto planes, auto ot) {
-                hipLaunchKernelGGL((k_reset<NT, decltype(planes)::value, decltype(ot)>), dim3(grid), dim3(NT), sh, s, p, games, maps, count);
-            });
-        } else if (kind == K_MASKS) {
-            hipLaunchKernelGGL((k_masks<NT>), dim3(grid), dim3(NT), sh, s, p);
-        } else if (kind == K_OUTPUTS) {
-            with_obs(p.partial_obs, p.obs_float, [&](auto planes, auto ot) {
-                hipLaunchKernelGGL((k_outputs<NT, decltype(planes)::value, decltype(ot)>), dim3(grid), dim3(NT), sh, s, p);
-            });
-        } else {
-            const bool fb = p.fuse_bots && NT > 64;
-            if (fb) sh = fb_lds_bytes(p.HW, p.W, NT, !p.partial_obs && p.early_bot);
-            launch_step<NT>(one_engine(p), grid, sh, s, p.partial_obs, p.obs_float, fb);
-        }
-        return hipGetLastError();
-    });
+// The per-game kernels' launch: a workgroup per game (grid of them) at the unfused step's
+// workgroup size and LDS carve.  kernel(NT as a compile-time constant) names the kernel,
+// whose arguments are the engine and args.
+template <typename F, typename... A>
+static hipError_t per_game(const EngineParams& p, int grid, hipStream_t s, F&& kernel, A... args) {
+    if (grid == 0) return hipSuccess;
+    const int NT = step_nt(p.HW, false);
+    hipLaunchKernelGGL(with_nt(NT, kernel), dim3(grid), dim3(NT), lds_bytes(p.HW, p.W, NT), s, p, args...);
+    return hipGetLastError();
 }
 
 // One step launch over n engines of equal planes, obs type and bot fusion, at the
 // widest member's workgroup size (a narrower map leaves lanes idle in the game
-// logic; every wave still streams outputs).  bots_first: every member's bot games
-// take the grid's first segments, then the selfplay games -- workgroups start in
-// grid order, so the longest chains (the fused bot after the tick) start first and
-// the short selfplay games fill the last round.
+// logic; every wave still streams outputs).  A single engine's step is a group of one
+// with bots_first.  bots_first: every member's bot games take the grid's first
+// segments, then the selfplay games: workgroups start in grid order, and a bot game's
+// chain (the fused bot after the tick) is the longest, so the short selfplay games fill
+// the last round (4096 selfplay + 4096 bot envs, 16x16: step 215 -> 196 us,
+// profiles/r03_ab/ab20_single_engine_bots_first/).
 static hipError_t step_group(const EngineParams* ps, int n, hipStream_t s, bool bots_first) {
     if (n < 1 || n > MRTS_STEP_GROUP_MAX) return hipErrorInvalidValue;
     const EngineParams& p0 = ps[0];
@@ -1786,25 +1750,25 @@ int mrts_debug_stamps(unsigned long long* out, int max_rows, int reset) {
 }
 #endif
 hipError_t mrts_engine_reset(const EngineParams* p, hipStream_t s, const int32_t* games, const int32_t* maps, int count) {
-    return mrts::dispatch(*p, mrts::K_RESET, s, games, maps, count);
+    return mrts::with_obs(p->partial_obs, p->obs_float, [&](auto planes, auto ot) {
+        auto k = [](auto nt) { return mrts::k_reset<decltype(nt)::value, decltype(planes)::value, decltype(ot)>; };
+        return mrts::per_game(*p, games ? count : p->G, s, k, games, maps, count);
+    });
 }
-hipError_t mrts_engine_masks(const EngineParams* p, hipStream_t s) { return mrts::dispatch(*p, mrts::K_MASKS, s, nullptr, nullptr, 0); }
+hipError_t mrts_engine_outputs(const EngineParams* p, hipStream_t s) {
+    return mrts::with_obs(p->partial_obs, p->obs_float, [&](auto planes, auto ot) {
+        return mrts::per_game(*p, p->G, s, [](auto nt) { return mrts::k_outputs<decltype(nt)::value, decltype(planes)::value, decltype(ot)>; });
+    });
+}
+hipError_t mrts_engine_masks(const EngineParams* p, hipStream_t s) {
+    return mrts::per_game(*p, p->G, s, [](auto nt) { return mrts::k_masks<decltype(nt)::value>; });
+}
 hipError_t mrts_engine_masks_packed(const EngineParams* p, hipStream_t s, int32_t* packed) {
-    const size_t sh = mrts_engine_lds_bytes(p->HW, p->W);
-    mrts::with_nt(mrts::step_nt(p->HW, false), [&](auto nt) {
-        hipLaunchKernelGGL(mrts::k_masks_packed<decltype(nt)::value>, dim3(p->G), dim3(decltype(nt)::value), sh, s, *p, packed);
-    });
-    return hipGetLastError();
+    return mrts::per_game(*p, p->G, s, [](auto nt) { return mrts::k_masks_packed<decltype(nt)::value>; }, packed);
 }
-hipError_t mrts_engine_outputs(const EngineParams* p, hipStream_t s) { return mrts::dispatch(*p, mrts::K_OUTPUTS, s, nullptr, nullptr, 0); }
 hipError_t mrts_engine_raw_obs(const EngineParams* p, hipStream_t s, int32_t* raw) {
-    const size_t sh = mrts_engine_lds_bytes(p->HW, p->W);
-    mrts::with_nt(mrts::step_nt(p->HW, false), [&](auto nt) {
-        hipLaunchKernelGGL(mrts::k_raw<decltype(nt)::value>, dim3(p->G), dim3(decltype(nt)::value), sh, s, *p, raw);
-    });
-    return hipGetLastError();
+    return mrts::per_game(*p, p->G, s, [](auto nt) { return mrts::k_raw<decltype(nt)::value>; }, raw);
 }
-hipError_t mrts_engine_step(const EngineParams* p, hipStream_t s) { return mrts::dispatch(*p, mrts::K_STEP, s, nullptr, nullptr, 0); }
 hipError_t mrts_engine_step_group(const EngineParams* ps, int n, hipStream_t s, int bots_first) {
     return mrts::step_group(ps, n, s, bots_first != 0);
 }

@@ -499,60 +499,40 @@ __global__ __launch_bounds__(PT) void k_unpack_masks(const int32_t* __restrict__
 }  // namespace mrts
 
 // The launchers take the caller's stream, allocate nothing and synchronise nothing.
+// `packed` picks the packed-mask kernel, which takes no src.
 extern "C" {
-hipError_t mrts_engine_policy_sample(const float* logits, const int32_t* mask, const int32_t* src, int n, int hw, int env0,
+using namespace mrts::policy;
+hipError_t mrts_engine_policy_sample(int packed, const float* logits, const int32_t* mask, const int32_t* src, int n, int hw, int env0,
                                      uint64_t seed, uint32_t step, int64_t* act, float* logprob, float* entropy, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(mrts::policy::k_policy_sample, dim3((unsigned)n), dim3(mrts::policy::PT), 0, s, logits, mask, src, hw, env0, seed,
-                       step, act, logprob, entropy);
+    if (packed) hipLaunchKernelGGL(k_policy_sample_packed, dim3((unsigned)n), dim3(PT), 0, s, logits, mask, hw, env0, seed, step, act, logprob, entropy);
+    else hipLaunchKernelGGL(k_policy_sample, dim3((unsigned)n), dim3(PT), 0, s, logits, mask, src, hw, env0, seed, step, act, logprob, entropy);
     return hipGetLastError();
 }
-hipError_t mrts_engine_policy_eval(const float* logits, const int32_t* mask, const int32_t* src, int n, int hw, const int64_t* act,
-                                   float* logprob, float* entropy, hipStream_t s) {
+hipError_t mrts_engine_policy_eval(int packed, const float* logits, const int32_t* mask, const int32_t* src, int n, int hw,
+                                   const int64_t* act, float* logprob, float* entropy, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(mrts::policy::k_policy_eval, dim3((unsigned)n), dim3(mrts::policy::PT), 0, s, logits, mask, src, hw, act, logprob,
-                       entropy);
+    if (packed) hipLaunchKernelGGL(k_policy_eval_packed, dim3((unsigned)n), dim3(PT), 0, s, logits, mask, hw, act, logprob, entropy);
+    else hipLaunchKernelGGL(k_policy_eval, dim3((unsigned)n), dim3(PT), 0, s, logits, mask, src, hw, act, logprob, entropy);
     return hipGetLastError();
 }
-hipError_t mrts_engine_policy_eval_bwd(const float* logits, const int32_t* mask, const int32_t* src, int n, int hw, const int64_t* act,
-                                       const float* g_lp, const float* g_ent, float* grad, hipStream_t s) {
+hipError_t mrts_engine_policy_eval_bwd(int packed, const float* logits, const int32_t* mask, const int32_t* src, int n, int hw,
+                                       const int64_t* act, const float* g_lp, const float* g_ent, float* grad, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(mrts::policy::k_policy_eval_bwd, dim3((unsigned)n), dim3(mrts::policy::PT), 0, s, logits, mask, src, hw, act, g_lp,
-                       g_ent, grad);
-    return hipGetLastError();
-}
-hipError_t mrts_engine_policy_sample_packed(const float* logits, const int32_t* packed, int n, int hw, int env0, uint64_t seed,
-                                            uint32_t step, int64_t* act, float* logprob, float* entropy, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(mrts::policy::k_policy_sample_packed, dim3((unsigned)n), dim3(mrts::policy::PT), 0, s, logits, packed, hw, env0,
-                       seed, step, act, logprob, entropy);
-    return hipGetLastError();
-}
-hipError_t mrts_engine_policy_eval_packed(const float* logits, const int32_t* packed, int n, int hw, const int64_t* act, float* logprob,
-                                          float* entropy, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(mrts::policy::k_policy_eval_packed, dim3((unsigned)n), dim3(mrts::policy::PT), 0, s, logits, packed, hw, act,
-                       logprob, entropy);
-    return hipGetLastError();
-}
-hipError_t mrts_engine_policy_eval_bwd_packed(const float* logits, const int32_t* packed, int n, int hw, const int64_t* act,
-                                              const float* g_lp, const float* g_ent, float* grad, hipStream_t s) {
-    if (n == 0) return hipSuccess;
-    hipLaunchKernelGGL(mrts::policy::k_policy_eval_bwd_packed, dim3((unsigned)n), dim3(mrts::policy::PT), 0, s, logits, packed, hw, act,
-                       g_lp, g_ent, grad);
+    if (packed) hipLaunchKernelGGL(k_policy_eval_bwd_packed, dim3((unsigned)n), dim3(PT), 0, s, logits, mask, hw, act, g_lp, g_ent, grad);
+    else hipLaunchKernelGGL(k_policy_eval_bwd, dim3((unsigned)n), dim3(PT), 0, s, logits, mask, src, hw, act, g_lp, g_ent, grad);
     return hipGetLastError();
 }
 // rows = n * hw >= 1 (mrts_capi.cpp: within the samplers' row bound, so the grid is below 2^23)
+static dim3 converter_grid(long long rows) { return dim3((unsigned)((rows + CV_ROWS - 1) / CV_ROWS)); }
 hipError_t mrts_engine_pack_masks(const int32_t* mask, const int32_t* src, long long rows, int32_t* packed, hipStream_t s) {
     if (rows == 0) return hipSuccess;
-    const unsigned grid = (unsigned)((rows + mrts::policy::CV_ROWS - 1) / mrts::policy::CV_ROWS);
-    hipLaunchKernelGGL(mrts::policy::k_pack_masks, dim3(grid), dim3(mrts::policy::PT), 0, s, mask, src, rows, packed);
+    hipLaunchKernelGGL(k_pack_masks, converter_grid(rows), dim3(PT), 0, s, mask, src, rows, packed);
     return hipGetLastError();
 }
 hipError_t mrts_engine_unpack_masks(const int32_t* packed, long long rows, int32_t* mask, int32_t* src, hipStream_t s) {
     if (rows == 0) return hipSuccess;
-    const unsigned grid = (unsigned)((rows + mrts::policy::CV_ROWS - 1) / mrts::policy::CV_ROWS);
-    hipLaunchKernelGGL(mrts::policy::k_unpack_masks, dim3(grid), dim3(mrts::policy::PT), 0, s, packed, rows, mask, src);
+    hipLaunchKernelGGL(k_unpack_masks, converter_grid(rows), dim3(PT), 0, s, packed, rows, mask, src);
     return hipGetLastError();
 }
 }

@@ -57,29 +57,6 @@ def _as_int32(t):
     return (t if t.dtype == torch.int32 else t.to(torch.int32)).contiguous()
 
 
-def _inputs(logits, mask, source, float_masks, actions=None):
-    """Check the three inputs; returns (logits, mask, source, N, HW) contiguous, mask / source int32."""
-    _need(logits, "logits", (torch.float32,))
-    mdt = (torch.int32, torch.float32) if float_masks else (torch.int32,)
-    _need(mask, "mask", mdt)
-    _need(source, "source", mdt)
-    if mask.dim() != 3 or mask.shape[2] != CHANNELS or mask.shape[1] < 1:
-        raise ValueError(f"mask must be [N, HW, {CHANNELS}], not {tuple(mask.shape)}")
-    n, hw = int(mask.shape[0]), int(mask.shape[1])
-    if tuple(source.shape) != (n, hw):
-        raise ValueError(f"source must be [N, HW] = {(n, hw)}, not {tuple(source.shape)}")
-    if tuple(logits.shape) not in ((n * hw, CHANNELS), (n, hw, CHANNELS)):
-        raise ValueError(f"logits must be [N*HW, {CHANNELS}] or [N, HW, {CHANNELS}] with N, HW = {(n, hw)}, not {tuple(logits.shape)}")
-    if actions is not None:
-        _need(actions, "actions", (torch.int64,))
-        if actions.numel() != n * hw * COMPONENTS:
-            raise ValueError(f"actions must hold N*HW*{COMPONENTS} = {n * hw * COMPONENTS} elements, not {tuple(actions.shape)}")
-        _on_gpu(logits, logits=logits, mask=mask, source=source, actions=actions)
-    else:
-        _on_gpu(logits, logits=logits, mask=mask, source=source)
-    return logits.contiguous(), _as_int32(mask), _as_int32(source), n, hw
-
-
 def _is_packed(mask):
     """A packed tensor by its shape: [N, HW, 3] (a dense mask ends in 78)."""
     return isinstance(mask, torch.Tensor) and mask.dim() == 3 and mask.shape[2] == PACKED_WORDS
@@ -98,6 +75,16 @@ def _format(mask, source):
     return False
 
 
+def _dense(mask, source):
+    """Check a dense pair's shapes; returns (N, HW)."""
+    if mask.dim() != 3 or mask.shape[2] != CHANNELS or mask.shape[1] < 1:
+        raise ValueError(f"mask must be [N, HW, {CHANNELS}], not {tuple(mask.shape)}")
+    n, hw = int(mask.shape[0]), int(mask.shape[1])
+    if tuple(source.shape) != (n, hw):
+        raise ValueError(f"source must be [N, HW] = {(n, hw)}, not {tuple(source.shape)}")
+    return n, hw
+
+
 def _packed(packed):
     """Check a packed tensor's type and shape; returns (N, HW)."""
     _need(packed, "packed", (torch.int32,))
@@ -106,24 +93,45 @@ def _packed(packed):
     return int(packed.shape[0]), int(packed.shape[1])
 
 
-def _inputs_packed(logits, packed, actions=None):
-    """_inputs for a packed call; returns (logits, packed, N, HW) contiguous."""
+def _inputs(logits, mask, source, float_masks, actions=None):
+    """Check a call's inputs, dense (mask and source) or packed (source is None: `mask` is the
+    packed words); returns (logits, mask, source or None, N, HW) contiguous, the masks int32."""
     _need(logits, "logits", (torch.float32,))
-    n, hw = _packed(packed)
+    if source is None:
+        n, hw = _packed(mask)
+        tensors = {"logits": logits, "packed": mask}
+    else:
+        mdt = (torch.int32, torch.float32) if float_masks else (torch.int32,)
+        _need(mask, "mask", mdt)
+        _need(source, "source", mdt)
+        n, hw = _dense(mask, source)
+        tensors = {"logits": logits, "mask": mask, "source": source}
     if tuple(logits.shape) not in ((n * hw, CHANNELS), (n, hw, CHANNELS)):
         raise ValueError(f"logits must be [N*HW, {CHANNELS}] or [N, HW, {CHANNELS}] with N, HW = {(n, hw)}, not {tuple(logits.shape)}")
     if actions is not None:
         _need(actions, "actions", (torch.int64,))
         if actions.numel() != n * hw * COMPONENTS:
             raise ValueError(f"actions must hold N*HW*{COMPONENTS} = {n * hw * COMPONENTS} elements, not {tuple(actions.shape)}")
-        _on_gpu(logits, logits=logits, packed=packed, actions=actions)
-    else:
-        _on_gpu(logits, logits=logits, packed=packed)
-    return logits.contiguous(), packed.contiguous(), n, hw
+        tensors["actions"] = actions
+    _on_gpu(logits, **tensors)
+    return logits.contiguous(), _as_int32(mask), None if source is None else _as_int32(source), n, hw
 
 
 def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
+
+
+def _head(name, logits, mask, source, *tail):
+    """Call the action head's entry point mrts_`name` (dense) or mrts_`name`_packed (source is
+    None) on the logits' device and current stream."""
+    dev = logits.device
+    if source is None:
+        name, masks = name + "_packed", (mask.data_ptr(),)
+    else:
+        masks = (mask.data_ptr(), source.data_ptr())
+    with torch.cuda.device(dev):
+        rc = getattr(_native.lib(), "mrts_" + name)(_stream(dev), logits.data_ptr(), *masks, *tail)
+    _native.check(rc, None, name)
 
 
 def pack_masks(mask, source):
@@ -132,11 +140,7 @@ def pack_masks(mask, source):
     non-source row's stray bits too."""
     _need(mask, "mask", (torch.int32,))
     _need(source, "source", (torch.int32,))
-    if mask.dim() != 3 or mask.shape[2] != CHANNELS or mask.shape[1] < 1:
-        raise ValueError(f"mask must be [N, HW, {CHANNELS}], not {tuple(mask.shape)}")
-    n, hw = int(mask.shape[0]), int(mask.shape[1])
-    if tuple(source.shape) != (n, hw):
-        raise ValueError(f"source must be [N, HW] = {(n, hw)}, not {tuple(source.shape)}")
+    n, hw = _dense(mask, source)
     _on_gpu(mask, mask=mask, source=source)
     dev = mask.device
     m, s = mask.contiguous(), source.contiguous()
@@ -169,36 +173,25 @@ def sample(logits, mask, source=None, *, seed, step, env0=0):
     step) under `seed` -- the stream of the engine's stand-in sampler, so a shard
     [env0, env0 + N) draws exactly its slice of one larger batch.  No grad.
     `mask` with `source`: the dense tensors; `mask` alone: packed [N, HW, 3] int32."""
-    packed = _format(mask, source)
-    if packed:
-        lg, m, n, hw = _inputs_packed(logits, mask)
-    else:
-        lg, m, s, n, hw = _inputs(logits, mask, source, False)
+    _format(mask, source)
+    lg, m, s, n, hw = _inputs(logits, mask, source, False)
     dev = lg.device
     actions = torch.empty((n, hw, COMPONENTS), dtype=torch.int64, device=dev)
     logprob = torch.empty((n,), dtype=torch.float32, device=dev)
     entropy = torch.empty((n,), dtype=torch.float32, device=dev)
-    tail = (n, hw, int(env0), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(step) & 0xFFFFFFFF, actions.data_ptr(),
-            logprob.data_ptr(), entropy.data_ptr())
-    with torch.cuda.device(dev):
-        if packed:
-            rc = _native.lib().mrts_policy_sample_packed(_stream(dev), lg.detach().data_ptr(), m.data_ptr(), *tail)
-        else:
-            rc = _native.lib().mrts_policy_sample(_stream(dev), lg.detach().data_ptr(), m.data_ptr(), s.data_ptr(), *tail)
-    _native.check(rc, None, "policy_sample")
+    _head("policy_sample", lg.detach(), m, s, n, hw, int(env0), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(step) & 0xFFFFFFFF,
+          actions.data_ptr(), logprob.data_ptr(), entropy.data_ptr())
     return actions, logprob, entropy
 
 
 class _Evaluate(torch.autograd.Function):
+    """`source` is None for packed masks, which `mask` then holds."""
+
     @staticmethod
     def forward(ctx, logits, mask, source, actions, n, hw):
-        dev = logits.device
-        logprob = torch.empty((n,), dtype=torch.float32, device=dev)
-        entropy = torch.empty((n,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _native.lib().mrts_policy_evaluate(_stream(dev), logits.data_ptr(), mask.data_ptr(), source.data_ptr(), n, hw,
-                                                    actions.data_ptr(), logprob.data_ptr(), entropy.data_ptr())
-        _native.check(rc, None, "policy_evaluate")
+        logprob = torch.empty((n,), dtype=torch.float32, device=logits.device)
+        entropy = torch.empty((n,), dtype=torch.float32, device=logits.device)
+        _head("policy_evaluate", logits, mask, source, n, hw, actions.data_ptr(), logprob.data_ptr(), entropy.data_ptr())
         ctx.save_for_backward(logits, mask, source, actions)
         ctx.shape = (n, hw)
         return logprob, entropy
@@ -207,53 +200,15 @@ class _Evaluate(torch.autograd.Function):
     def backward(ctx, g_lp, g_ent):
         logits, mask, source, actions = ctx.saved_tensors
         n, hw = ctx.shape
-        dev = logits.device
         zero = None
         if g_lp is None or g_ent is None:
-            zero = torch.zeros((n,), dtype=torch.float32, device=dev)
+            zero = torch.zeros((n,), dtype=torch.float32, device=logits.device)
         g_lp = zero if g_lp is None else g_lp.to(torch.float32).contiguous()
         g_ent = zero if g_ent is None else g_ent.to(torch.float32).contiguous()
         grad = torch.empty_like(logits)   # the kernel writes every element
-        with torch.cuda.device(dev):
-            rc = _native.lib().mrts_policy_evaluate_backward(_stream(dev), logits.data_ptr(), mask.data_ptr(), source.data_ptr(), n, hw,
-                                                             actions.data_ptr(), g_lp.data_ptr(), g_ent.data_ptr(), grad.data_ptr())
-        _native.check(rc, None, "policy_evaluate_backward")
+        _head("policy_evaluate_backward", logits, mask, source, n, hw, actions.data_ptr(), g_lp.data_ptr(), g_ent.data_ptr(),
+              grad.data_ptr())
         return grad, None, None, None, None, None
-
-
-class _EvaluatePacked(torch.autograd.Function):
-    """_Evaluate over packed masks: saves the packed tensor, calls the packed backward."""
-
-    @staticmethod
-    def forward(ctx, logits, packed, actions, n, hw):
-        dev = logits.device
-        logprob = torch.empty((n,), dtype=torch.float32, device=dev)
-        entropy = torch.empty((n,), dtype=torch.float32, device=dev)
-        with torch.cuda.device(dev):
-            rc = _native.lib().mrts_policy_evaluate_packed(_stream(dev), logits.data_ptr(), packed.data_ptr(), n, hw,
-                                                           actions.data_ptr(), logprob.data_ptr(), entropy.data_ptr())
-        _native.check(rc, None, "policy_evaluate_packed")
-        ctx.save_for_backward(logits, packed, actions)
-        ctx.shape = (n, hw)
-        return logprob, entropy
-
-    @staticmethod
-    def backward(ctx, g_lp, g_ent):
-        logits, packed, actions = ctx.saved_tensors
-        n, hw = ctx.shape
-        dev = logits.device
-        zero = None
-        if g_lp is None or g_ent is None:
-            zero = torch.zeros((n,), dtype=torch.float32, device=dev)
-        g_lp = zero if g_lp is None else g_lp.to(torch.float32).contiguous()
-        g_ent = zero if g_ent is None else g_ent.to(torch.float32).contiguous()
-        grad = torch.empty_like(logits)   # the kernel writes every element
-        with torch.cuda.device(dev):
-            rc = _native.lib().mrts_policy_evaluate_backward_packed(_stream(dev), logits.data_ptr(), packed.data_ptr(), n, hw,
-                                                                    actions.data_ptr(), g_lp.data_ptr(), g_ent.data_ptr(),
-                                                                    grad.data_ptr())
-        _native.check(rc, None, "policy_evaluate_backward_packed")
-        return grad, None, None, None, None
 
 
 def evaluate(logits, mask, source=None, actions=None):
@@ -265,8 +220,6 @@ def evaluate(logits, mask, source=None, actions=None):
     [N, HW, 3] int32, as it comes out of the rollout buffer."""
     if actions is None:
         raise TypeError("evaluate() needs the actions to evaluate")
-    if _format(mask, source):
-        lg, p, n, hw = _inputs_packed(logits, mask, actions)
-        return _EvaluatePacked.apply(lg, p, actions.contiguous(), n, hw)
+    _format(mask, source)
     lg, m, s, n, hw = _inputs(logits, mask, source, True, actions)
     return _Evaluate.apply(lg, m, s, actions.contiguous(), n, hw)

@@ -84,6 +84,29 @@ def test_unbound_calls_fail_loudly():
     assert rc != 0 and b"not bound" in _native.lib().mrts_last_error(h)
 
 
+def test_step_entry_points_front_checks():
+    """The three step entry points on a created but unbound handle: MRTS_ESTATE with
+    "not bound" in mrts_last_error and no launch; mrts_step with a null handle:
+    MRTS_ESTATE; mrts_step_group with a null handle list: MRTS_EINVAL."""
+    from gym_microrts import _native
+
+    lib = _native.lib()
+    EINVAL, ESTATE, P = -1, -5, ctypes.c_void_p(4096)   # P: a non-null address, never dereferenced
+    h = _create()
+    assert lib.mrts_step(h, None, P, P, P, P, P) == ESTATE
+    assert b"not bound" in lib.mrts_last_error(h)
+    assert lib.mrts_reset(h, None, None) != 0 and b"reset" in lib.mrts_last_error(h)   # another message in between
+    assert lib.mrts_step_weighted(h, None, P, P, P, P, P, P, P) == ESTATE
+    assert b"not bound" in lib.mrts_last_error(h)
+    lib.mrts_reset(h, None, None)
+    hs, io = (ctypes.c_void_p * 1)(h), (_native.StepIO * 1)(_native.StepIO(*[4096] * 7))
+    assert lib.mrts_step_group(hs, 1, None, io, _native.GROUP_BOTS_FIRST) == ESTATE
+    assert b"not bound" in lib.mrts_last_error(h)
+    assert lib.mrts_step(None, None, P, P, P, P, P) == ESTATE
+    assert lib.mrts_step_group(None, 1, None, io, 0) == EINVAL
+    lib.mrts_destroy(h)
+
+
 def test_sampler_and_head_entry_points_check_their_arguments():
     """The three stand-in samplers and the three action-head entry points share one
     argument check and return before any launch: MRTS_EINVAL for a null pointer, for
