@@ -64,46 +64,38 @@ struct BL {   // LDS of one bot game
     uint32_t* fw;     // free-cell words (bot_fw_words)
 };
 
-__host__ __device__ inline size_t b16(size_t x) { return (x + 15) & ~(size_t)15; }
 // free-cell words: two per 64 cells (one ballot) + a zero word past the last cell
-__host__ __device__ inline size_t bot_fw_words(int HW) { return (size_t)(HW + 63) / 64 * 2 + 1; }
-// `tail`: where the small arrays (pend, pab, vis, sc, fw) go when the caller keeps
-// them apart (the fused k_step's early bot, whose workgroup still reads the
-// step's scalars and visibility words while the bot runs); null = behind wall
-__host__ __device__ inline size_t bot_tail_bytes(int HW, int W) {
-    const size_t posw = (size_t)(HW + 2 * W) / 32 + 1;
-    return 2 * b16(4 * posw) + b16(4 * ((size_t)HW / 32 + 1)) + b16(4 * 4) + b16(4 * bot_fw_words(HW));
+__host__ __device__ inline int bot_fw_words(int HW) { return (HW + 63) / 64 * 2 + 1; }
+// The bot's layout in two pieces, so that the fused k_step can place them itself (fused_carve,
+// mrts_engine.hip): the core overlays the step's arrays (unit uid act at the same offsets), the small
+// arrays go wherever `c` stands.  k_bot's own layout is bot_carve: core, terrain, small arrays.
+__host__ __device__ inline void bot_carve_core(Carver& c, BL& L, int HW) {
+    L.unit = c.take<uint32_t>(HW);
+    L.uid = c.take<int32_t>(HW);
+    L.act = c.take<uint32_t>(HW);
+    L.ucell = c.take<int32_t>(HW);
+    L.uuid = c.take<int32_t>(HW);
+    L.pa = c.take<int32_t>(HW);
+    L.aa = c.take<int4>(2 * (size_t)HW);
 }
-// unit uid act ucell uuid pa + the abstract actions (the fused step's region)
-__host__ __device__ inline size_t bot_core_bytes(int HW) { return b16(4 * (size_t)HW) * 6 + b16(32 * (size_t)HW); }
-__host__ __device__ inline size_t bot_lds_bytes(int HW, int W) {
-    return bot_core_bytes(HW) + b16((size_t)HW) + bot_tail_bytes(HW, W);
+__host__ __device__ inline void bot_carve_tail(Carver& c, BL& L, int HW, int W) {
+    L.pend = c.take<uint32_t>(pos_words(HW, W));
+    L.pab = c.take<uint32_t>(pos_words(HW, W));
+    L.vis = c.take<uint32_t>(vis_words(HW));
+    L.sc = c.take<int>(4);   // pending produce cost per player, error bits, units
+    L.fw = c.take<uint32_t>(bot_fw_words(HW));
 }
-// own_wall = false: no terrain slot (the fused bot reads the step's terrain in place)
-__host__ __device__ inline BL bot_carve(unsigned char* base, int HW, int W, unsigned char* tail = nullptr, bool own_wall = true) {
+// bytes: the layout's size, when asked for
+__host__ __device__ inline BL bot_carve(unsigned char* base, int HW, int W, size_t* bytes = nullptr) {
     BL L;
-    size_t o = 0;
-    auto take = [&](size_t n) { unsigned char* p = base + o; o += b16(n); return p; };
-    const size_t posw = (size_t)(HW + 2 * W) / 32 + 1;
-    L.unit = (uint32_t*)take(4 * (size_t)HW);
-    L.uid = (int32_t*)take(4 * (size_t)HW);
-    L.act = (uint32_t*)take(4 * (size_t)HW);
-    L.ucell = (int32_t*)take(4 * (size_t)HW);
-    L.uuid = (int32_t*)take(4 * (size_t)HW);
-    L.pa = (int32_t*)take(4 * (size_t)HW);
-    L.aa = (int4*)take(32 * (size_t)HW);
-    L.wall = own_wall ? (uint8_t*)take((size_t)HW) : nullptr;
-    if (tail) {
-        base = tail;
-        o = 0;
-    }
-    L.pend = (uint32_t*)take(4 * posw);
-    L.pab = (uint32_t*)take(4 * posw);
-    L.vis = (uint32_t*)take(4 * ((size_t)HW / 32 + 1));
-    L.sc = (int*)take(4 * 4);   // pending produce cost per player, error bits, units
-    L.fw = (uint32_t*)take(4 * bot_fw_words(HW));
+    Carver c{base};
+    bot_carve_core(c, L, HW);
+    L.wall = c.take<uint8_t>(HW);
+    bot_carve_tail(c, L, HW, W);
+    if (bytes) *bytes = c.o;
     return L;
 }
+__host__ __device__ inline size_t bot_lds_bytes(int HW, int W) { size_t n; bot_carve(lds_any_base(), HW, W, &n); return n; }
 
 // wave-uniform scalar state (identical in every lane) + the lane's grid row
 struct BS {
@@ -1153,7 +1145,7 @@ __device__ __forceinline__ void random_biased_get_action(BS& S, const BL& L) {
     // pa.ru starts as the usage of every pending assignment
     S.pa_res[0] = S.pend_res[0];
     S.pa_res[1] = S.pend_res[1];
-    const int posw = (S.HW + 2 * S.W) / 32 + 1;
+    const int posw = pos_words(S.HW, S.W);
     for (int i = blane(); i < posw; i += BT) L.pab[i] = L.pend[i];
     for_each_unit(S, L, [&](int, uint32_t u, uint32_t a) { return u_owner(u) == S.player && a == 0; }, [&](const URef& ur) {
         const int c = ur.c;
@@ -1186,7 +1178,7 @@ __device__ __forceinline__ void random_single_get_action(BS& S, const BL& L) {
     if (ni == 0) return;
     S.pa_res[0] = S.pend_res[0];
     S.pa_res[1] = S.pend_res[1];
-    const int posw = (S.HW + 2 * S.W) / 32 + 1;
+    const int posw = pos_words(S.HW, S.W);
     for (int i = blane(); i < posw; i += BT) L.pab[i] = L.pend[i];
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     uint32_t ctr[4] = {0xFFFFFFFFu, S.tick, (uint32_t)S.game, 0x52534E47u + (uint32_t)(1 - S.player)};
@@ -1221,18 +1213,17 @@ __device__ __forceinline__ void bot_sync() {
 
 // ---- the kernel ------------------------------------------------------------------------
 // ai.getAction(player, gs) of bot game b, by ONE wavefront (lanes = blane()
-// 0..63), LDS at `smem` (bot_lds_bytes).  FUSED: run by wave 0 of a k_step
+// 0..63), LDS carved as `L`.  FUSED: run by wave 0 of a k_step
 // workgroup for the NEXT tick while the other waves stream the outputs (no
 // workgroup barriers here then; the game state was stored before the caller's
 // last barrier); otherwise the body of k_bot (a one-wave workgroup).
-// FUSED: `tail` (the small arrays' region) and `step_wall` (the step's terrain,
-// read in place) are the fused k_step layout's (mrts_engine.hip fb_*_offset).
+// L: bot_carve for k_bot; FUSED, the fused k_step layout's (mrts_engine.hip
+// fused_carve: the small arrays apart, `wall` the step's terrain, read in place).
 
 template <bool FUSED>
-__device__ __forceinline__ void bot_game(const EngineParams& p, int b, int player, unsigned char* smem,
+__device__ __forceinline__ void bot_game(const EngineParams& p, int b, int player, const BL& L,
                                          const int32_t* step_sc = nullptr, bool pre_ok = false, int4 pre_aa = int4{0, 0, 0, 0},
-                                         int4 pre_aa2 = int4{0, 0, 0, 0}, unsigned char* tail = nullptr,
-                                         const uint8_t* step_wall = nullptr, bool preset = false) {
+                                         int4 pre_aa2 = int4{0, 0, 0, 0}, bool preset = false) {
     const int g = p.nsp_games + b, lane = blane();
     const int HW = p.HW, W = p.W;
     int32_t* genv = p.genv + (size_t)g * MRTS_GENV_WORDS;
@@ -1247,9 +1238,6 @@ __device__ __forceinline__ void bot_game(const EngineParams& p, int b, int playe
         if (lane0()) genv[w_npa] = 0;
         return;
     }
-    BL L = bot_carve(smem, HW, W, tail, step_wall == nullptr);
-    // the fused bot reads the step's terrain in place (the waves beside it read it too)
-    if (step_wall) L.wall = const_cast<uint8_t*>(step_wall);
     int4* const aa_g = p.aa + ((size_t)b * 2 + player) * HW * 2;
     int32_t* const pa_g = p.botpa + ((size_t)b * 2 + player) * HW;
     S.W = W;
@@ -1268,10 +1256,10 @@ __device__ __forceinline__ void bot_game(const EngineParams& p, int b, int playe
     S.npa = 0;
     S.pa_res[0] = S.pa_res[1] = 0;
     const int map = gs[MRTS_G_MAP];
-    const int posw = (HW + 2 * W) / 32 + 1, visw = HW / 32 + 1;
+    const int posw = pos_words(HW, W), visw = vis_words(HW);
     // Fused: the step kernel's unit / uid / act arrays sit at the bot's offsets
     // (both carves start unit, uid, act of 4*HW bytes at smem 0) and hold the
-    // state it has just stored -- no reload.
+    // state it has just stored -- no reload -- and the terrain is the step's.
     // Fused, the first 128 abstract-action words come prefetched in registers
     // (pre_aa / pre_aa2: words lane, lane + 64).
     // preset (the fused k_step's early bot, full observability): the workgroup has
@@ -1283,8 +1271,8 @@ __device__ __forceinline__ void bot_game(const EngineParams& p, int b, int playe
             L.unit[c] = (uint32_t)v.x;
             L.uid[c] = v.y;
             L.act[c] = (uint32_t)v.z;
+            L.wall[c] = p.map_wall[(size_t)map * HW + c];
         }
-        if (!step_wall) L.wall[c] = p.map_wall[(size_t)map * HW + c];
     }
     for (int i = lane; !preset && i < posw; i += BT) L.pend[i] = L.pab[i] = 0;
     for (int i = lane; !preset && i < visw; i += BT) L.vis[i] = 0;

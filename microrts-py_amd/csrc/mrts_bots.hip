@@ -23,7 +23,7 @@ __global__ __launch_bounds__(BT) void k_bot(EngineParams p) {
         if (b < 0) return;   // a selfplay game
     }
     if (game_parked(p, p.nsp_games + b)) return;
-    bot_game<false>(p, b, player, smem);
+    bot_game<false>(p, b, player, bot_carve(smem, p.HW, p.W));
 }
 
 }  // namespace bots

@@ -218,7 +218,7 @@ static void masks_written(mrts_vec *h, hipError_t e, bool dense) {
 // delta needs a bit per cell and view in one register of the lane that owns the cell: at
 // most 16 cells per lane of the narrowest step workgroup (every map mrts_create accepts)
 static bool delta_ok(const mrts_vec *h) {
-    return h->mask_delta && h->masks_synced && h->next_mask && h->HW <= 16 * mrts_engine_step_nt(h->HW, 0);
+    return h->mask_delta && h->masks_synced && h->next_mask && h->HW <= 16 * mrts_engine_step_layout(h->HW, h->W, 0, 0, 0).NT;
 }
 
 static int fail(mrts_vec *h, int code, const std::string &msg) {
@@ -289,7 +289,7 @@ int mrts_create(const mrts_config *cfg, mrts_vec **out) {
     h->W = h->maps[0].w;
     h->H = h->maps[0].h;
     h->HW = h->W * h->H;
-    if (mrts_engine_lds_bytes(h->HW, h->W) > 65536)
+    if (mrts_engine_step_layout(h->HW, h->W, 0, 0, 0).lds_bytes > MRTS_LDS_CAP)
         return fail(h, MRTS_ENOTIMPL, "map too large: the step kernel's workgroup LDS carve exceeds 64 KB (maps up to "
                                       "about 1128 cells fit, e.g. 32x32, 33x33, 47x24; DESIGN.md §3)");
     h->game_map.assign(h->ngames, 0);
@@ -320,7 +320,7 @@ int mrts_create(const mrts_config *cfg, mrts_vec **out) {
     if (h->nbot_active) {
         if (h->W > 32 || h->H > 64)
             return fail(h, MRTS_ENOTIMPL, "device bots need maps at most 32 wide and 64 high (one bit word per row)");
-        if (mrts_engine_bot_lds_bytes(h->HW, h->W) > 65536)
+        if (mrts_engine_bot_lds_bytes(h->HW, h->W) > MRTS_LDS_CAP)
             return fail(h, MRTS_ENOTIMPL, "map too large for the bot kernel's LDS");
     }
     size_t o = 0;
@@ -393,7 +393,6 @@ int mrts_bind_workspace(mrts_vec *h, void *dev, void *stream) {
     p.botpa = h->nbot_active ? (int32_t *)(h->ws + h->off_botpa) : nullptr;
     p.nbot_active = h->nbot_active;
     p.game_offset = h->game_offset;
-    p.early_bot = mrts_engine_early_bot_ok(h->HW, h->W);
     p.parked = nullptr;   // until a game is parked
     h->parked.assign(h->ngames, 0);
     h->err.clear();
@@ -416,7 +415,7 @@ static bool bound(mrts_vec *h) { return h && h->ws; }
 // workgroup (the fused step workgroup has at least two waves: maps of <= 64
 // cells take 128 lanes, mrts_engine.hip step_nt).
 static bool fused(const mrts_vec *h) {
-    return h->fuse && h->nbot_active > 0 && h->nbot0 == 0 && mrts_engine_fused_lds_bytes(h->HW, h->W, h->partial_obs) <= 163840;
+    return h->fuse && h->nbot_active > 0 && h->nbot0 == 0 && mrts_engine_step_layout(h->HW, h->W, 1, h->partial_obs, 0).lds_bytes <= MRTS_LDS_CAP_FUSED;
 }
 
 // after a reset of every game (games == null) or of the listed ones: with
@@ -528,26 +527,30 @@ int mrts_set_reward_weight(mrts_vec *h, const double *w, int32_t shaping) {
 #ifndef MRTS_GROUP_MIN_WG_PER_CU
 #define MRTS_GROUP_MIN_WG_PER_CU 6
 #endif
-static const size_t kGroupLdsCap = 163840 / MRTS_GROUP_MIN_WG_PER_CU;
+static const size_t kGroupLdsCap = MRTS_LDS_CAP_FUSED / MRTS_GROUP_MIN_WG_PER_CU;
 
 // Launch plan of a group: launch_of[i] = the launch (0, 1, ..) member i runs in.
 // Members of equal planes / obs type / fusion share a launch (merge != 0), each
 // launch in the caller's order of its first member.  Returns the launch count.
 static int group_plan(const EngineParams *ps, int n, int policy, int *launch_of) {
     const int merge = policy & 3;
-    auto lds = [&](const EngineParams &p, int NT) { return mrts_engine_group_lds_bytes(p.HW, p.W, p.fuse_bots, NT, p.partial_obs); };
+    auto lds = [&](const EngineParams &p, int NT) { return mrts_engine_step_layout(p.HW, p.W, p.fuse_bots, p.partial_obs, NT).lds_bytes; };
     auto compatible = [&](const EngineParams &a, const EngineParams &b) {
         return a.partial_obs == b.partial_obs && a.obs_float == b.obs_float && (a.fuse_bots != 0) == (b.fuse_bots != 0);
     };
-    for (int i = 0; i < n; i++) launch_of[i] = -1;
+    int own_nt[MRTS_STEP_GROUP_MAX];   // each member's own workgroup size, asked once
+    for (int i = 0; i < n; i++) {
+        launch_of[i] = -1;
+        own_nt[i] = mrts_engine_step_layout(ps[i].HW, ps[i].W, ps[i].fuse_bots, ps[i].partial_obs, 0).NT;
+    }
     int nl = 0;
     for (int i = 0; i < n; i++) {
         if (launch_of[i] >= 0) continue;
-        int NT = mrts_engine_step_nt(ps[i].HW, ps[i].fuse_bots);
+        int NT = own_nt[i];
         launch_of[i] = nl;
         for (int j = i + 1; merge && j < n; j++) {
             if (launch_of[j] >= 0 || !compatible(ps[i], ps[j])) continue;
-            const int NT2 = std::max(NT, mrts_engine_step_nt(ps[j].HW, ps[j].fuse_bots));
+            const int NT2 = std::max(NT, own_nt[j]);
             bool fits = true;
             if (merge == MRTS_GROUP_MERGE_FIT)
                 for (int k = 0; k < n; k++)
@@ -980,9 +983,10 @@ int mrts_error_flags(mrts_vec *h, void *stream, int32_t *flags_out) {
 int mrts_fused_layout_ok(int32_t width, int32_t height) {
     if (width <= 0 || height <= 0 || width > 32 || height > 64) return -1;
     const int HW = width * height;
-    if (mrts_engine_fused_lds_bytes(HW, width, 0) > 163840) return -1;
-    if (mrts_engine_bot_lds_bytes(HW, width) > 65536) return -1;   // mrts_create refuses such bot engines
-    return mrts_engine_early_bot_ok(HW, width);
+    const mrts_step_layout_t l = mrts_engine_step_layout(HW, width, 1, 0, 0);
+    if (l.lds_bytes > MRTS_LDS_CAP_FUSED) return -1;
+    if (mrts_engine_bot_lds_bytes(HW, width) > MRTS_LDS_CAP) return -1;   // mrts_create refuses such bot engines
+    return l.early;
 }
 
 const char *mrts_utt_json(const mrts_vec *h) { return h ? h->utt.c_str() : ""; }

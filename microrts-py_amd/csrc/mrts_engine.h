@@ -40,6 +40,60 @@ __shared__ int mrts_stamp_row;
 #define MRTS_STAMP_ADD(k, v, cond) do { } while (0)
 #endif
 
+// One workgroup's LDS: an unfused step or a k_bot workgroup stays within the 64 KB a HIP kernel gets
+// without asking; the bot-fused step may take a CU's whole 160 KB.
+#define MRTS_LDS_CAP 65536
+#define MRTS_LDS_CAP_FUSED 163840
+
+namespace mrts {
+// LDS carving (all dynamic, 16-byte aligned pieces: cdna_hip_programming §6 G17).  A layout is ONE carve
+// function that takes its arrays from a Carver in order: the pointers are the kernels', the end offset is
+// the layout's size, and a SpanLog (host-side checks) receives each array's extent as it is taken.
+__host__ __device__ inline size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
+// a wave-uniform offset as one scalar the compiler keeps rather than recomputes (the host: the value itself)
+__host__ __device__ inline size_t lds_uniform(size_t o) {
+#ifdef __HIP_DEVICE_COMPILE__
+    return (size_t)(unsigned)__builtin_amdgcn_readfirstlane((int)o);
+#else
+    return o;
+#endif
+}
+struct Span {
+    const unsigned char* p;
+    size_t n;   // the bytes asked for (the slot is a16(n))
+};
+struct SpanLog {
+    enum { MAX = 48 };
+    Span s[MAX];
+    int n = 0;
+    __host__ __device__ Span of(const void* p) const {   // the array that starts at p; {null, 0}: not logged
+        for (int i = 0; i < n; i++) if (s[i].p == p) return s[i];
+        return Span{nullptr, 0};
+    }
+};
+struct Carver {
+    unsigned char* base;
+    size_t o = 0;
+    SpanLog* log = nullptr;
+    template <typename T>
+    __host__ __device__ T* take(size_t count) {
+        unsigned char* p = base + o;
+        if (log && log->n < SpanLog::MAX) log->s[log->n++] = Span{p, count * sizeof(T)};
+        o += a16(count * (size_t)sizeof(T));
+        return reinterpret_cast<T*>(p);
+    }
+};
+// sizes are offsets: a carve runs on any base
+__host__ __device__ inline unsigned char* lds_any_base() { return reinterpret_cast<unsigned char*>((size_t)1 << 20); }
+
+// A move / produce targets position x + y * W + W, unchecked: 0 .. HW + 2 W - 1, one bit each.
+// The three word counts differ by up to one word:
+__host__ __device__ inline int pos_words_live(int HW, int W) { return (HW + 2 * W + 31) / 32; }   // words that hold a position
+__host__ __device__ inline int pos_words(int HW, int W) { return (HW + 2 * W) / 32 + 1; }   // claim, bot pend / pab: + 1 when whole
+__host__ __device__ inline int posbits_words(int HW, int W) { return pos_words_live(HW, W) + 1; }   // Lds::posbits: a spare word
+__host__ __device__ inline int vis_words(int HW) { return HW / 32 + 1; }   // one player's visibility bits
+}  // namespace mrts
+
 struct EngineParams {
     int4 *cells;            // [G][cstride] (the first HW records of each game's row)
     int cstride;            // int4 records between consecutive games' cells (>= HW)
@@ -76,7 +130,8 @@ struct EngineParams {
     int bot_ngames;
     int fuse_bots;          // k_step: wave 0 of each bot game's workgroup decides the next tick's bot actions
     int game_offset;        // global index of game 0 (a shard of a larger batch): keys the bots' RNG
-    int early_bot;          // fused k_step: the bot may start beside phase A (mrts_engine_early_bot_ok for this size)
+    int early_bot;          // fused k_step: the bot may start beside phase A; set by the step launch for its
+                            // workgroup size (mrts_engine_step_layout's `early`), not by the engine's owner
     const uint8_t *parked;  // [G] 1 = parked (mrts_park_games): no tick, no masks / bots, zero outputs at
                             // reset; null while no game was ever parked
 };
@@ -99,8 +154,13 @@ hipError_t mrts_engine_reset(const EngineParams *p, hipStream_t s, const int32_t
 hipError_t mrts_engine_masks(const EngineParams *p, hipStream_t s);
 hipError_t mrts_engine_outputs(const EngineParams *p, hipStream_t s);
 hipError_t mrts_engine_step_group(const EngineParams *ps, int n, hipStream_t s, int bots_first);
-size_t mrts_engine_group_lds_bytes(int HW, int W, int fused, int NT, int partial);
-int mrts_engine_step_nt(int HW, int fused);
+// The step workgroup of a map size: NT lanes (NT = 0 in: the size's own, else a launch's), its dynamic LDS
+// (the end of the step carve, or of the fused carve) and whether the fused bot starts beside phase A.
+struct mrts_step_layout_t {
+    int NT, early;
+    size_t lds_bytes;
+};
+mrts_step_layout_t mrts_engine_step_layout(int HW, int W, int fused, int partial, int NT);
 hipError_t mrts_engine_bots(const EngineParams *p, hipStream_t s);
 hipError_t mrts_engine_raw_obs(const EngineParams *p, hipStream_t s, int32_t *raw);
 // mrts_sampler.hip: the stand-in samplers (n * hw within 32 bits, actions 16-byte aligned: mrts_capi.cpp checks)
@@ -123,9 +183,6 @@ hipError_t mrts_engine_unpack_masks(const int32_t *packed, long long rows, int32
 // mrts_engine.hip again (mrts_engine_bot_lds_bytes: mrts_bots.hip)
 hipError_t mrts_engine_masks_packed(const EngineParams *p, hipStream_t s, int32_t *packed);
 hipError_t mrts_engine_render(const EngineParams *p, hipStream_t s, int game, int map, int size, uint8_t *rgb);
-size_t mrts_engine_lds_bytes(int HW, int W);
 size_t mrts_engine_bot_lds_bytes(int HW, int W);
-size_t mrts_engine_fused_lds_bytes(int HW, int W, int partial);
-int mrts_engine_early_bot_ok(int HW, int W);
 }
 #endif

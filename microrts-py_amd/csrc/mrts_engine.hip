@@ -40,7 +40,7 @@
 namespace mrts {
 
 // ---------------------------------------------------------------------------
-// LDS carving (all dynamic, 16-byte aligned pieces: cdna_hip_programming §6 G17)
+// The step workgroup's LDS (Carver: mrts_engine.h)
 struct Lds {
     uint32_t* unit;
     int32_t* uid;
@@ -58,8 +58,8 @@ struct Lds {
     uint8_t* wall;
     unsigned long long* ballot;
     uint32_t* posbits;
-    uint32_t* claim;   // [2][posw] target positions claimed by >= 1 / >= 2 rows this tick
-    uint32_t* vis;   // [2][HW/32+1] cells observable by player 0 / 1 (partial obs)
+    uint32_t* claim;   // [2][pos_words] target positions claimed by >= 1 / >= 2 rows this tick
+    uint32_t* vis;   // [2][vis_words] cells observable by player 0 / 1 (partial obs)
     int* sc;         // scalars
 };
 // L.sc[0 .. MRTS_GENV_WORDS) mirrors genv (load_game / store_game)
@@ -83,87 +83,91 @@ __device__ __forceinline__ void st16(void* dst, int a, int b, int c, int d) {
     *reinterpret_cast<v4i*>(dst) = v;
 }
 
-__host__ __device__ inline size_t a16(size_t x) { return (x + 15) & ~(size_t)15; }
-
-// L.vis: both players' visibility words (phase A), and before that the ballot
-// words of the step's first compaction (one 8-B word per wave and NT cells)
-__host__ __device__ inline size_t vis_bytes(int HW, int NT) {
-    const size_t v = 8 * (size_t)(HW / 32 + 1), b = 8 * (size_t)((HW + NT - 1) / NT) * (NT / 64);
-    return v > b ? v : b;
+// The step layout.  b0: the blist0 array (player 0's bot PlayerAction: bot-vs-bot games,
+// which are never bot-fused); own_wall: the terrain array (the fused step keeps it apart,
+// fused_carve sets L.wall).  The layout's size is c.o afterwards.
+__host__ __device__ inline Lds carve(Carver& c, int HW, int W, int NT, bool b0 = true, bool own_wall = true) {
+    Lds L;
+    L.unit = c.take<uint32_t>(HW);
+    L.uid = c.take<int32_t>(HW);
+    L.act = c.take<uint32_t>(HW);
+    L.seq = c.take<uint32_t>(HW);
+    L.aux = c.take<uint32_t>(HW);
+    L.resv = c.take<int32_t>(HW);
+    L.list = c.take<int32_t>(HW);
+    L.prod = c.take<int32_t>(HW);
+    L.blist = c.take<int32_t>(HW);
+    // (!b0: unreachable by construction -- fused engines have no player-0 bots, mrts_capi fused())
+    L.blist0 = b0 ? c.take<int32_t>(HW) : L.blist;
+    L.snap = c.take<int4>(HW);
+    L.outw = (uint32_t*)L.resv;   // resv, list, prod, blist, [blist0,] snap: >= 32 B per cell, contiguous
+    L.outm = L.outw + 2 * HW;
+    L.wall = own_wall ? c.take<uint8_t>(HW) : nullptr;
+    const size_t ballots = (size_t)((HW + NT - 1) / NT) * (NT / 64);   // one 8-B word per wave and NT cells
+    L.ballot = c.take<unsigned long long>(ballots + 1);
+    L.posbits = c.take<uint32_t>(posbits_words(HW, W));
+    L.sc = c.take<int>(SC_WORDS);
+    // both players' visibility words (phase A), and before that the ballot words of the step's first compaction
+    const size_t visw = vis_words(HW);
+    L.vis = c.take<uint32_t>(2 * (visw > ballots ? visw : ballots));
+    L.claim = c.take<uint32_t>(2 * (size_t)pos_words(HW, W));
+    return L;
 }
-
-// b0: the blist0 array (player 0's bot PlayerAction: bot-vs-bot games, which are
-// never bot-fused); wall: the terrain array (the fused step keeps it apart, at
-// fb_wall_offset)
-__host__ __device__ inline size_t lds_bytes(int HW, int W, int NT, bool b0 = true, bool wall = true) {
-    size_t b = 0;
-    b += a16(4 * (size_t)HW) * (b0 ? 10 : 9); // unit uid act seq aux resv list prod blist [blist0]
-    b += a16(16 * (size_t)HW);     // snap
-    b += wall ? a16((size_t)HW) : 0;
-    b += a16(8 * (size_t)((HW + NT - 1) / NT) * (NT / 64) + 8);
-    b += a16(4 * (size_t)((HW + 2 * W + 31) / 32 + 1));
-    b += a16(4 * SC_WORDS);
-    b += a16(vis_bytes(HW, NT));
-    b += a16(8 * (size_t)((HW + 2 * W) / 32 + 1));
-    return b;
+__host__ __device__ inline Lds carve(unsigned char* base, int HW, int W, int NT) {
+    Carver c{base};
+    return carve(c, HW, W, NT);
 }
 
 // Bot-fused k_step layout (24x24 52.3 KB -> 40.1 KB, 3 -> 4
-// workgroups per CU):
+// workgroups per CU), everything a fused workgroup needs, carved once:
 //   [0, core)   the step's arrays (no blist0, no terrain) until phase A, the
 //               bot's (unit uid act ucell uuid pa, abstract actions) afterwards
-//   outw        a bot game's output words: it streams them while wave 0 runs the
+//   words       a bot game's output words: it streams them while wave 0 runs the
 //               bot, so they lie outside the bot's region -- its mask words (one
 //               view, 12 B per cell) here, its one-hot words (4 B per cell) in the
 //               step's uid array on the early path (the bot reads uids only in its
 //               setup, which the workgroup builds before the waves split), else
 //               here behind the mask words
 //   tail        the bot's small arrays (pend pab vis sc fw)
-//   counter     the streaming waves' phase-A meeting point (early path)
+//   early_cnt   the streaming waves' phase-A meeting point (early path)
 //   wall        the terrain, read in place by the step, phase A and the bot
-// Selfplay games of a fused launch run no bot and alias their output words onto
-// the step's dead arrays, as the unfused kernel does.  `early`: the engine takes
-// the early path (full observability and early_bot_disjoint).
-__host__ __device__ inline size_t fb_outw_offset(int HW, int W, int NT) {
-    const size_t a = lds_bytes(HW, W, NT, false, false), b = bots::bot_core_bytes(HW);
-    return a16(a > b ? a : b);
-}
-__host__ __device__ inline size_t fb_tail_offset(int HW, int W, int NT, bool early) {
-    return fb_outw_offset(HW, W, NT) + a16((early ? 12 : 16) * (size_t)HW);
-}
-__host__ __device__ inline size_t fb_early_cnt_offset(int HW, int W, int NT, bool early) {
-    return fb_tail_offset(HW, W, NT, early) + a16(bots::bot_tail_bytes(HW, W));
-}
-__host__ __device__ inline size_t fb_wall_offset(int HW, int W, int NT, bool early) { return fb_early_cnt_offset(HW, W, NT, early) + 16; }
-__host__ __device__ inline size_t fb_lds_bytes(int HW, int W, int NT, bool early) {
-    return fb_wall_offset(HW, W, NT, early) + a16((size_t)HW);
-}
-
-__host__ __device__ inline Lds carve(unsigned char* base, int HW, int W, int NT, bool b0 = true, uint8_t* wall = nullptr) {
+// bot_game = false: a selfplay game of a fused launch, which runs no bot and aliases
+// its output words onto the step's dead arrays, as the unfused kernel does.  `early`:
+// the engine takes the early path (full observability and early_bot_disjoint).
+struct FusedLds {
     Lds L;
-    size_t o = 0;
-    auto take = [&](size_t n) { unsigned char* p = base + o; o += a16(n); return p; };
-    L.unit = (uint32_t*)take(4 * (size_t)HW);
-    L.uid = (int32_t*)take(4 * (size_t)HW);
-    L.act = (uint32_t*)take(4 * (size_t)HW);
-    L.seq = (uint32_t*)take(4 * (size_t)HW);
-    L.aux = (uint32_t*)take(4 * (size_t)HW);
-    L.resv = (int32_t*)take(4 * (size_t)HW);
-    L.list = (int32_t*)take(4 * (size_t)HW);
-    L.prod = (int32_t*)take(4 * (size_t)HW);
-    L.blist = (int32_t*)take(4 * (size_t)HW);
-    // (!b0: unreachable by construction -- fused engines have no player-0 bots, mrts_capi fused())
-    L.blist0 = b0 ? (int32_t*)take(4 * (size_t)HW) : L.blist;
-    L.snap = (int4*)take(16 * (size_t)HW);
-    L.outw = (uint32_t*)L.resv;   // resv, list, prod, blist, [blist0,] snap: >= 32 B per cell, contiguous
-    L.outm = L.outw + 2 * HW;
-    L.wall = wall ? wall : (uint8_t*)take((size_t)HW);
-    L.ballot = (unsigned long long*)take(8 * (size_t)((HW + NT - 1) / NT) * (NT / 64) + 8);
-    L.posbits = (uint32_t*)take(4 * (size_t)((HW + 2 * W + 31) / 32 + 1));
-    L.sc = (int*)take(4 * SC_WORDS);
-    L.vis = (uint32_t*)take(vis_bytes(HW, NT));
-    L.claim = (uint32_t*)take(8 * (size_t)((HW + 2 * W) / 32 + 1));
-    return L;
+    uint32_t* words;       // the output words' region (a bot game's L.outm / L.outw)
+    uint32_t* tail;        // the bot's small arrays, tail_words of them: zeroed for the early bot
+    int tail_words;
+    int* early_cnt;
+    size_t bytes;
+    bots::BL B;            // the bot's arrays: its core over the step's, its small arrays in the tail, the step's terrain
+};
+// step_log: the extents of F.L's arrays, the words, the counter and the terrain; bot_log: of F.B's own arrays
+// (two logs: the step's and the bot's arrays start at the same addresses)
+__host__ __device__ inline FusedLds fused_carve(unsigned char* base, int HW, int W, int NT, bool early, bool bot_game,
+                                                SpanLog* step_log = nullptr, SpanLog* bot_log = nullptr) {
+    FusedLds F;
+    Carver c{base, 0, step_log}, cb{base, 0, bot_log};
+    F.L = carve(c, HW, W, NT, false, false);
+    bots::bot_carve_core(cb, F.B, HW);
+    c.o = cb.o = c.o > cb.o ? c.o : cb.o;
+    F.words = c.take<uint32_t>((early ? 3 : 4) * (size_t)HW);
+    if (bot_game) {
+        F.L.outw = early ? reinterpret_cast<uint32_t*>(F.L.uid) : F.words;
+        F.L.outm = early ? F.words : F.words + HW;
+    }
+    // the tail's offset as one scalar: left as a sum, the compiler rebuilds the whole chain (64-bit adds of
+    // spilled terms and the max above) in front of every bot loop that walks a small array
+    cb.o = c.o = lds_uniform(c.o);
+    F.tail = reinterpret_cast<uint32_t*>(base + cb.o);
+    bots::bot_carve_tail(cb, F.B, HW, W);
+    F.tail_words = (int)((cb.o - c.o) / 4);
+    c.o = cb.o;
+    F.early_cnt = c.take<int>(1);
+    F.L.wall = F.B.wall = c.take<uint8_t>(HW);
+    F.bytes = c.o;
+    return F;
 }
 
 // The early-bot k_step (FB, P == 29): while wave 0 runs bots::bot_game (its
@@ -172,34 +176,33 @@ __host__ __device__ inline Lds carve(unsigned char* base, int HW, int W, int NT,
 // / wall / scalars and writes the output words (one-hot into the uid array, mask
 // words behind the bot's region) and the meeting counter.  True when, for this
 // map size, the bot writes none of those bytes and phase A writes none the bot
-// reads -- computed from the two carves themselves -- and the bot's unit / uid /
-// act arrays are the step's (it reads the state just stored in place).  The host
-// takes the early path only then (EngineParams::early_bot; mrts_fused_layout_ok).
+// reads -- every extent is the one the fused carve took -- and the bot's unit / uid /
+// act arrays are the step's (it reads the state just stored in place).  The step
+// launch takes the early path only then (EngineParams::early_bot; mrts_fused_layout_ok).
 __host__ __device__ inline bool early_bot_disjoint(int HW, int W, int NT) {
-    unsigned char* const z = reinterpret_cast<unsigned char*>((size_t)1 << 20);   // any base: only offsets matter
-    const Lds S = carve(z, HW, W, NT, false, z + fb_wall_offset(HW, W, NT, true));
-    const bots::BL B = bots::bot_carve(z, HW, W, z + fb_tail_offset(HW, W, NT, true), false);
-    struct R {
-        const void* p;
-        size_t n;
-    };
-    auto lo = [&](const R& r) { return (size_t)((const unsigned char*)r.p - z); };
-    auto overlap = [&](const R& a, const R& b) { return lo(a) < lo(b) + b.n && lo(b) < lo(a) + a.n; };
-    const size_t hw = (size_t)HW, posw = (size_t)(HW + 2 * W) / 32 + 1, visw = (size_t)HW / 32 + 1;
+    SpanLog step, bot;
+    const FusedLds F = fused_carve(lds_any_base(), HW, W, NT, true, true, &step, &bot);
+    const Lds& S = F.L;
+    const bots::BL& B = F.B;
+    auto overlap = [](const Span& a, const Span& b) { return a.p < b.p + b.n && b.p < a.p + a.n; };
     if (B.unit != S.unit || B.uid != S.uid || B.act != S.act) return false;
-    const R bot_w[9] = {{B.ucell, 4 * hw}, {B.uuid, 4 * hw}, {B.pa, 4 * hw}, {B.aa, 32 * hw},
-                        {B.pend, 4 * posw}, {B.pab, 4 * posw}, {B.vis, 4 * visw}, {B.sc, 16},
-                        {B.fw, 4 * bots::bot_fw_words(HW)}};
-    const R bot_r[3] = {{B.unit, 4 * hw}, {B.act, 4 * hw}, {S.wall, hw}};   // (uids: read by the setup only)
-    const R a_r[3] = {{S.unit, 4 * hw}, {S.act, 4 * hw}, {S.wall, hw}};      // (resources: in registers)
-    const R a_w[3] = {{S.uid, 4 * hw}, {z + fb_outw_offset(HW, W, NT), 12 * hw}, {z + fb_early_cnt_offset(HW, W, NT, true), 4}};
-    for (const R& b : bot_w) {
-        if (lo(b) + b.n > fb_lds_bytes(HW, W, NT, true)) return false;
-        for (const R& a : a_r) if (overlap(a, b)) return false;
-        for (const R& a : a_w) if (overlap(a, b)) return false;
+    const Span bot_w[9] = {bot.of(B.ucell), bot.of(B.uuid), bot.of(B.pa), bot.of(B.aa), bot.of(B.pend),
+                           bot.of(B.pab), bot.of(B.vis), bot.of(B.sc), bot.of(B.fw)};
+    const Span bot_r[3] = {bot.of(B.unit), bot.of(B.act), step.of(B.wall)};   // (uids: read by the setup only)
+    const Span a_r[3] = {step.of(S.unit), step.of(S.act), step.of(S.wall)};   // (resources: in registers)
+    const Span a_w[3] = {step.of(S.uid), step.of(F.words), step.of(F.early_cnt)};
+    auto missing = [](const Span* t, int n) {
+        for (int i = 0; i < n; i++) if (!t[i].p) return true;
+        return false;
+    };   // an array the logs do not hold would go unchecked: fail closed
+    if (missing(bot_w, 9) || missing(bot_r, 3) || missing(a_r, 3) || missing(a_w, 3)) return false;
+    for (const Span& b : bot_w) {
+        if (b.p + b.n > lds_any_base() + F.bytes) return false;
+        for (const Span& a : a_r) if (overlap(a, b)) return false;
+        for (const Span& a : a_w) if (overlap(a, b)) return false;
     }
-    for (const R& a : a_w)
-        for (const R& b : bot_r) if (overlap(a, b)) return false;
+    for (const Span& a : a_w)
+        for (const Span& b : bot_r) if (overlap(a, b)) return false;
     return true;
 }
 
@@ -251,10 +254,8 @@ __device__ __forceinline__ int compact_cells(int HW, F pred, int32_t* list, unsi
 // wave then starts at the abstract actions (bot_game, preset).  Full observability
 // only (the early path's condition), so the bot's view is the state itself.
 template <int NT>
-__device__ __forceinline__ void bot_setup_workgroup(const EngineParams& p, unsigned char* smem, unsigned char* tail,
-                                                    const uint8_t* wall) {
+__device__ __forceinline__ void bot_setup_workgroup(const EngineParams& p, const bots::BL& B) {
     const int HW = p.HW, W = p.W, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const bots::BL B = bots::bot_carve(smem, HW, W, tail, false);
     // unit list by cell (B.pa), its uids alongside (the first words of B.aa, rewritten
     // by the bot later); B.sc[3] (zeroed with the tail) counts them
     int32_t* const ucells = B.pa;
@@ -264,7 +265,7 @@ __device__ __forceinline__ void bot_setup_workgroup(const EngineParams& p, unsig
         bool fr = false;
         if (c < HW) {
             const uint32_t u = B.unit[c], a = B.act[c];
-            fr = !wall[c] && u == 0;
+            fr = !B.wall[c] && u == 0;
             if (u != 0) {
                 const int pos = atomicAdd(&B.sc[3], 1);
                 ucells[pos] = c;
@@ -366,7 +367,7 @@ __device__ __forceinline__ void store_game(const EngineParams& p, const Lds& L, 
 // atomic (or_sight_disk).
 template <int NT>
 __device__ __forceinline__ void compute_vis(const EngineParams& p, const Lds& L) {
-    const int HW = p.HW, nw = HW / 32 + 1;
+    const int HW = p.HW, nw = vis_words(HW);
     for (int i = threadIdx.x; i < 2 * nw; i += NT) L.vis[i] = 0;
     __syncthreads();
     for (int c = threadIdx.x; c < HW; c += NT) {
@@ -381,7 +382,7 @@ __device__ __forceinline__ void compute_vis(const EngineParams& p, const Lds& L)
 // phase A's one-hot word of cell c for every view of the game (into L.outw)
 template <int P>
 __device__ __forceinline__ void onehot_words(const EngineParams& p, const Lds& L, const Game& G, int c) {
-    const int HW = p.HW, nw = HW / 32 + 1;
+    const int HW = p.HW, nw = vis_words(HW);
     const uint32_t u = L.unit[c], a = L.act[c];
     const uint8_t wl = L.wall[c];
     for (int v = 0; v < G.nviews; v++) {
@@ -552,7 +553,7 @@ __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L
                                              int res1, int skip = 0, int* early_cnt = nullptr, bool delta = false) {
     const int HW = p.HW;
     if (skip == 0 && obs && masks) {
-        const int nw = HW / 32 + 1;
+        const int nw = vis_words(HW);
         for (int c = threadIdx.x; c < HW; c += NT) mask_words(p, L, G, c, res0, res1, delta);
         if (P == 31)
             for (int i = threadIdx.x; i < 2 * nw; i += NT) L.vis[i] = 0;
@@ -594,7 +595,7 @@ __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L
     // Bot-fused k_step (skip = 64): from here on wave 0 runs bots::bot_game, whose
     // LDS region starts at smem offset 0 and overwrites the step's arrays but the
     // unit / act / wall it reads and, on the early path, the uid array.  Phase B
-    // must read nothing but the output words `ow` / `mw` (fb_outw_offset) and
+    // must read nothing but the output words `ow` / `mw` (FusedLds::words) and
     // kernel parameters.
     if ((int)threadIdx.x < skip) return;
     MRTS_STAMP(8, (int)threadIdx.x == skip);
@@ -663,7 +664,7 @@ __global__ __launch_bounds__(NT) void k_raw(EngineParams p, int32_t* raw) {
     Lds L = carve(smem, p.HW, p.W, NT);
     const int g = blockIdx.x, HW = p.HW;
     const Game G = game_of(p, g);
-    const int PR = p.partial_obs ? 7 : 6, nw = HW / 32 + 1;
+    const int PR = p.partial_obs ? 7 : 6, nw = vis_words(HW);
     if (game_parked(p, g)) {   // a parked game's envs read zero (mrts_park_games)
         int32_t* out = raw + (size_t)G.env0 * PR * HW;
         for (int i = threadIdx.x; i < G.nviews * PR * HW; i += NT) out[i] = 0;
@@ -801,7 +802,7 @@ __device__ __forceinline__ void issue_player(const EngineParams& p, const Lds& L
                              bool vector) {
     const int time = L.sc[SC_TIME];
     // --- fromVectorAction: ResourceUsage.consistentWith(pa.ru) ----------------
-    const int nposw = (gd.HW + 2 * gd.W + 31) / 32;
+    const int nposw = pos_words_live(gd.HW, gd.W);
     for (int i = 0; i < nposw; i++) L.posbits[i] = 0;
     int pa_cost = 0;
     for (int i = 0; vector && i < n; i++) {
@@ -1121,21 +1122,17 @@ __device__ __forceinline__ void commit_game(const EngineParams& p, const Lds& L,
 // slower: hipcc allocates 164 VGPRs for the looped body).
 // FB (bot fusion, p.fuse_bots): in a bot game's workgroup, wave 0 decides the
 // NEXT tick's bot actions (bots::bot_game on the state just stored) while waves
-// 1.. stream this tick's outputs; its LDS follows the step's (launch_all).
+// 1.. stream this tick's outputs; the workgroup's LDS is then the fused layout (fused_carve).
 template <int NT, int P, typename OT, bool FB>
 __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const int HW = p.HW;
     const bool early_layout = FB && P == 29 && p.early_bot;
-    Lds L = carve(smem, HW, p.W, NT, !FB, FB ? smem + fb_wall_offset(HW, p.W, NT, early_layout) : nullptr);
     const bool botg = FB && g >= p.nsp_games && NT > 64;   // the workgroup runs the next tick's bot
-    if (botg) {   // the output words outside the bot's region (fb_outw_offset)
-        uint32_t* const region = reinterpret_cast<uint32_t*>(smem + fb_outw_offset(HW, p.W, NT));
-        L.outw = early_layout ? reinterpret_cast<uint32_t*>(L.uid) : region;
-        L.outm = early_layout ? region : region + HW;
-    }
-    int* const early_cnt = reinterpret_cast<int*>(smem + fb_early_cnt_offset(HW, p.W, NT, early_layout));
-    if (FB && threadIdx.x == 0) *early_cnt = 0;   // read after several barriers below
+    const bool early = early_layout && botg;                // ... beside phase A
+    const FusedLds F = FB ? fused_carve(smem, HW, p.W, NT, early_layout, botg) : FusedLds{carve(smem, HW, p.W, NT)};
+    const Lds& L = F.L;
+    if (FB && threadIdx.x == 0) *F.early_cnt = 0;   // read after several barriers below
     // issue priority: the game logic (latency-bound chains of LDS steps and
     // barriers) over other workgroups' output streams (memory-bound), which
     // drop to 0 in emit_outputs' phase B
@@ -1164,17 +1161,15 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     if (pf_ok) prefetch_game<NT, FB>(p, g, pf);
     else if (pf_wide) prefetch_wide<NT>(p, game_of(p, g), g, wpf);
     MRTS_STAMP(15, threadIdx.x == 0);
-    if (FB && P == 29 && p.early_bot && g >= p.nsp_games && NT > 64) {   // the early bot's tail arrays start zeroed
-        uint32_t* t = reinterpret_cast<uint32_t*>(smem + fb_tail_offset(HW, p.W, NT, true));
-        for (int i = threadIdx.x; i < (int)(bots::bot_tail_bytes(HW, p.W) / 4); i += NT) t[i] = 0;
-    }
+    if (early)   // the early bot's tail arrays start zeroed
+        for (int i = threadIdx.x; i < F.tail_words; i += NT) F.tail[i] = 0;
     const Game G = game_of(p, g);
     // Barriers: each phase below is ordered after the last one that wrote what it
     // reads from OTHER lanes; a phase that reads only its own lane's cells (the
     // same c = threadIdx.x + k * NT walk) follows its predecessor without one.
     // Everything zeroed or initialised here is first read after commit_game's barrier.
     if (threadIdx.x < SC_WORDS) L.sc[threadIdx.x] = 0;
-    const int posw = (HW + 2 * p.W) / 32 + 1;   // position words (targets as x + y * W + W)
+    const int posw = pos_words(HW, p.W);
     for (int i = threadIdx.x; i < 2 * posw; i += NT) L.claim[i] = 0;
     // the source-unit rows of this lane's first cell, fetched in the same round
     // trip as the game state (the decode below needs both)
@@ -1537,8 +1532,6 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     // the bot behind its barrier (the step's arrays are dead by then: only L.outw is
     // read on).  One bot_game call site for both: the inlined bot is most of this
     // kernel's code.
-    const bool early = early_layout && botg;
-    unsigned char* const tail = smem + fb_tail_offset(HW, p.W, NT, early_layout);
     // Delta masks: the rows the bound buffer holds from the last tick (the loaded state's
     // source rows) are marked in the mask words' region -- dead scratch lists, or a bot
     // game's own region -- by the lane that met the cell in the decode; phase A reads the
@@ -1549,15 +1542,15 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
             for (int v = 0; v < G.nviews; v++) L.outm[3 * (v * HW + c) + 2] = ((was_src >> (2 * k + v)) & 1u) ? MASK_ROW_STORE : 0u;
     if (early) {
         __syncthreads();
-        bot_setup_workgroup<NT>(p, smem, tail, L.wall);
+        bot_setup_workgroup<NT>(p, F.B);
         __syncthreads();
         MRTS_STAMP(14, threadIdx.x == 0);
     }
     if (!early || threadIdx.x >= 64)
-        emit_outputs<NT, P, OT>(p, L, G, true, p.mask != nullptr, res0, res1, botg ? 64 : 0, early ? early_cnt : nullptr, delta);
+        emit_outputs<NT, P, OT>(p, L, G, true, p.mask != nullptr, res0, res1, botg ? 64 : 0, early ? F.early_cnt : nullptr, delta);
     if (FB && botg && threadIdx.x < 64) {
         if (early) __builtin_amdgcn_s_setprio(3);   // the latency-bound bot wave first; the streaming waves are memory-bound
-        bots::bot_game<true>(p, g - p.nsp_games, 1, smem, L.sc, pf_ok, pf.aa, pf.aa2, tail, L.wall, early);
+        bots::bot_game<true>(p, g - p.nsp_games, 1, F.B, L.sc, pf_ok, pf.aa, pf.aa2, early);
         MRTS_STAMP(13, threadIdx.x == 0);
     }
 }
@@ -1675,8 +1668,8 @@ static void launch_step(const StepGroup& sg, int grid, size_t sh, hipStream_t s,
 template <typename F, typename... A>
 static hipError_t per_game(const EngineParams& p, int grid, hipStream_t s, F&& kernel, A... args) {
     if (grid == 0) return hipSuccess;
-    const int NT = step_nt(p.HW, false);
-    hipLaunchKernelGGL(with_nt(NT, kernel), dim3(grid), dim3(NT), lds_bytes(p.HW, p.W, NT), s, p, args...);
+    const mrts_step_layout_t l = mrts_engine_step_layout(p.HW, p.W, 0, 0, 0);
+    hipLaunchKernelGGL(with_nt(l.NT, kernel), dim3(grid), dim3(l.NT), l.lds_bytes, s, p, args...);
     return hipGetLastError();
 }
 
@@ -1703,10 +1696,11 @@ static hipError_t step_group(const EngineParams* ps, int n, hipStream_t s, bool 
     for (int i = 0; i < n; i++) {
         EngineParams& e = sg.e[i];
         e = ps[i];
-        if (fused) e.early_bot = early_bot_disjoint(e.HW, e.W, NT) ? 1 : 0;   // the layout at this launch's NT
-        sh = std::max(sh, fused ? fb_lds_bytes(e.HW, e.W, NT, !e.partial_obs && e.early_bot) : lds_bytes(e.HW, e.W, NT));
+        const mrts_step_layout_t l = mrts_engine_step_layout(e.HW, e.W, fused, e.partial_obs, NT);   // at this launch's NT
+        e.early_bot = l.early;
+        sh = std::max(sh, l.lds_bytes);
     }
-    if (sh > 163840) return hipErrorInvalidValue;   // one workgroup's LDS on a CU
+    if (sh > MRTS_LDS_CAP_FUSED) return hipErrorInvalidValue;   // one workgroup's LDS on a CU
     int grid = 0;
     auto seg = [&](int m, int g0, int g1) {
         if (g1 <= g0) return;
@@ -1772,22 +1766,22 @@ hipError_t mrts_engine_raw_obs(const EngineParams* p, hipStream_t s, int32_t* ra
 hipError_t mrts_engine_step_group(const EngineParams* ps, int n, hipStream_t s, int bots_first) {
     return mrts::step_group(ps, n, s, bots_first != 0);
 }
-size_t mrts_engine_group_lds_bytes(int HW, int W, int fused, int NT, int partial) {
-    return fused ? mrts::fb_lds_bytes(HW, W, NT, !partial && mrts::early_bot_disjoint(HW, W, NT)) : mrts::lds_bytes(HW, W, NT);
+mrts_step_layout_t mrts_engine_step_layout(int HW, int W, int fused, int partial, int NT) {
+    mrts_step_layout_t r{NT ? NT : mrts::step_nt(HW, fused != 0), 0, 0};
+    r.early = fused && !partial && mrts::early_bot_disjoint(HW, W, r.NT);
+    if (fused) {
+        r.lds_bytes = mrts::fused_carve(mrts::lds_any_base(), HW, W, r.NT, r.early != 0, true).bytes;
+    } else {
+        mrts::Carver c{mrts::lds_any_base()};
+        mrts::carve(c, HW, W, r.NT);
+        r.lds_bytes = c.o;
+    }
+    return r;
 }
-int mrts_engine_step_nt(int HW, int fused) { return mrts::step_nt(HW, fused != 0); }
 hipError_t mrts_engine_render(const EngineParams* p, hipStream_t s, int game, int map, int size, uint8_t* rgb) {
     const int nblk = (size * size + 255) / 256;
     hipLaunchKernelGGL(mrts::k_render, dim3(nblk), dim3(256), 0, s, p->cells + (size_t)game * p->cstride, p->map_wall + (size_t)map * p->HW,
                        p->W, p->H, size, rgb);
     return hipGetLastError();
-}
-int mrts_engine_early_bot_ok(int HW, int W) { return mrts::early_bot_disjoint(HW, W, mrts::step_nt(HW, true)) ? 1 : 0; }
-size_t mrts_engine_fused_lds_bytes(int HW, int W, int partial) {
-    const int NT = mrts::step_nt(HW, true);
-    return mrts::fb_lds_bytes(HW, W, NT, !partial && mrts::early_bot_disjoint(HW, W, NT));
-}
-size_t mrts_engine_lds_bytes(int HW, int W) {
-    return mrts::lds_bytes(HW, W, mrts::step_nt(HW, false));
 }
 }

@@ -151,6 +151,20 @@ def lib():
     return _lib
 
 
+class StepLayout(ctypes.Structure):
+    """mrts_step_layout_t (csrc/mrts_engine.h): the one ctypes statement of it."""
+    _fields_ = [("NT", ctypes.c_int), ("early", ctypes.c_int), ("lds_bytes", ctypes.c_size_t)]
+
+
+def step_layout(hw, w, fused=0, partial=0, nt=0):
+    """The internal layout query (diagnostics and tests; not part of the public header): the step
+    workgroup's lanes, dynamic LDS bytes and early-bot flag for a map of hw cells, w wide, at
+    nt lanes (0: the size's own)."""
+    q = lib().mrts_engine_step_layout
+    q.restype, q.argtypes = StepLayout, [ctypes.c_int] * 5
+    return q(hw, w, fused, partial, nt)
+
+
 def check(rc, handle=None, what="call"):
     if rc != MRTS_OK:
         msg = lib().mrts_last_error(handle).decode() if handle else ""

@@ -201,6 +201,39 @@ def test_fused_early_bot_layout_is_race_free_for_every_size():
     assert f(8, 8) == 1 and f(4, 4) == 1 and f(33, 16) == -1 and f(0, 5) == -1
 
 
+def test_lds_layout_bytes_are_pinned():
+    """The step, bot and fused LDS layouts are stated once (one carve each) and their sizes are
+    the carves' end offsets.  These rows were read from a build of the commit before that change
+    (profiles/lds_layout/): an array added to a carve moves them, and a size that does not follow
+    its carve is an out-of-bounds LDS access that no GPU test is guaranteed to hit."""
+    from gym_microrts import _native
+
+    bot = _native.lib().mrts_engine_bot_lds_bytes
+    bot.restype, bot.argtypes = ctypes.c_size_t, [ctypes.c_int] * 2
+
+    def lay(w, h, fused=0, partial=0, NT=0):
+        r = _native.step_layout(w * h, w, fused, partial, NT)
+        return r.NT, r.lds_bytes, r.early
+
+    # 8x8: its own workgroup is 64 lanes unfused, 128 fused; a wider launch's ballot words cost a few bytes
+    assert lay(8, 8) == (64, 3904, 0) and lay(8, 8, NT=256) == (256, 3936, 0)
+    assert lay(8, 8, fused=1) == (128, 4528, 1) and lay(8, 8, fused=1, NT=256) == (256, 4544, 1)
+    #        (w, h): unfused, fused, fused + fog, bot
+    rows = {(15, 15): (13344, 15792, 16688, 13072), (16, 16): (15008, 17888, 18912, 14800),
+            (24, 24): (33520, 40096, 42400, None), (32, 32): (59376, 71264, 75360, 58960),
+            (47, 24): (65408, None, None, None), (33, 33): (63296, None, None, None)}
+    for (w, h), (unfused, fused, fog, b) in rows.items():
+        assert lay(w, h) == (256, unfused, 0), (w, h)
+        if fused is not None:
+            assert lay(w, h, fused=1) == (256, fused, 1), (w, h)
+            assert lay(w, h, fused=1, partial=1) == (256, fog, 0), (w, h)   # fog: never the early path
+        if b is not None:
+            assert bot(w * h, w) == b, (w, h)
+    assert lay(47, 24)[1] <= 65536 < lay(48, 24)[1]   # the 64 KB limit of mrts_create
+    for w, h in [(8, 8), (47, 24), (33, 33)]:   # the early flag at the size's own fused workgroup
+        assert lay(w, h, fused=1)[2] == 1, (w, h)
+
+
 def test_step_group_plan_merges_what_fits():
     """mrts_step_group_plan (host logic, no workspace needed): configs[4]'s buckets -- 8x8
     and 16x16 share a launch under merge-fit (members that keep >= 6 workgroups per CU),

@@ -120,12 +120,11 @@ def large_case(seed):
     """A random shape past 32x32 that mrts_create still accepts (1025..1128 cells: the step's
     unprefetched path, tests/test_max_map_sizes.py), bots only where they are allowed (at
     most 32 wide and 64 high)."""
-    import ctypes
-
     from gym_microrts import _native
 
-    f = _native.lib().mrts_engine_lds_bytes
-    f.restype, f.argtypes = ctypes.c_size_t, [ctypes.c_int, ctypes.c_int]
+    def f(hw, w):   # the unfused step's LDS at the size's own workgroup size
+        return _native.step_layout(hw, w).lds_bytes
+
     rng = np.random.default_rng(7000 + seed)
     while True:
         w, h = int(rng.integers(12, 72)), int(rng.integers(12, 72))
