@@ -19,6 +19,10 @@ envs) runs end to end on the GPU.
   --api tensor : return_tensors=True, every buffer stays in HBM
 
   --head torch : the masked categorical head in torch ops (`policy()` below), the default
+  --obs packed : the engine writes one 32-bit one-hot word per cell (obs_format="packed") and the
+                 rollout buffer keeps those -- 4 bytes a cell against 116 / 124 -- unpacking
+                 them (gym_microrts.packed_obs) for each forward; --api tensor only
+
   --head fused : gym_microrts.policy_head -- the head as HIP kernels that read only the
                  rows of cells holding a unit that can act (sample in the rollout,
                  evaluate + its backward in the update); --api tensor only
@@ -51,7 +55,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "microrts-py_amd"))
 
-from gym_microrts import microrts_ai, policy_head  # noqa: E402
+from gym_microrts import microrts_ai, packed_obs, policy_head  # noqa: E402
 from gym_microrts.envs.vec_env import MicroRTSGridModeVecEnv  # noqa: E402
 from gym_microrts.run_driver import install as _install_compat  # noqa: E402
 
@@ -217,12 +221,16 @@ def bot_list(n):
 
 
 def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, updates=2, api="numpy", minibatches=4,
-        epochs=2, seed=1, device="cuda", log=print, max_steps=2000, head="torch", keep_first_rollout=False, masks="dense"):
+        epochs=2, seed=1, device="cuda", log=print, max_steps=2000, head="torch", keep_first_rollout=False, masks="dense",
+        obs="dense"):
     """head: "torch" or "fused" (policy_fused; --api tensor only).  keep_first_rollout: the
     returned stats carry "first_rollout" -- the first rollout's buffers and the weights
     that acted in it.  masks: "dense", or "packed" (--head fused only): the rollout buffer
     holds get_action_mask_packed()'s 12-byte rows instead of the 316 bytes of mask +
-    source, and the update gathers and evaluates from them."""
+    source, and the update gathers and evaluates from them.  obs: "dense", or "packed"
+    (--api tensor only): the engine writes the packed obs words, the buffer holds them
+    ([T, N, H, W] int32) and every forward reads packed_obs.unpack_obs of them -- the same
+    float32 planes the dense run sees."""
     if head not in ("torch", "fused"):
         raise ValueError(f"head must be 'torch' or 'fused', not {head!r}")
     if head == "fused" and api != "tensor":
@@ -231,6 +239,11 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
         raise ValueError(f"masks must be 'dense' or 'packed', not {masks!r}")
     if masks == "packed" and head != "fused":
         raise ValueError("--masks packed needs --head fused: only the fused head reads packed masks")
+    if obs not in ("dense", "packed"):
+        raise ValueError(f"obs must be 'dense' or 'packed', not {obs!r}")
+    if obs == "packed" and api != "tensor":
+        raise ValueError("--obs packed needs --api tensor: the packed words are unpacked on the device")
+    packed_o = obs == "packed"
     fused = head == "fused"
     packed = masks == "packed"
     torch.manual_seed(seed)
@@ -254,12 +267,21 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
                                              ai2s=bot_list(num_bot_envs) if num_bot_envs else [],
                                              map_paths=["maps/16x16/basesWorkers16x16A.xml"],
                                              reward_weight=np.array([10.0, 1.0, 1.0, 0.2, 1.0, 4.0]),
-                                             cycle_maps=["maps/16x16/basesWorkers16x16A.xml"], device=dev, return_tensors=True)
+                                             cycle_maps=["maps/16x16/basesWorkers16x16A.xml"], device=dev, return_tensors=True,
+                                             obs_format=obs)
     n, hw = envs.num_envs, envs.height * envs.width
     h, w, planes = envs.observation_space.shape
     net = GridNet(planes, h, w).to(dev)
     opt = torch.optim.Adam(net.parameters(), lr=2.5e-4, eps=1e-5)
-    buf_obs = torch.zeros((num_steps, n, h, w, planes), device=dev)
+    if packed_o:   # the words; `dense_obs` is the one dense tensor the rollout's forwards unpack into
+        buf_obs = torch.zeros((num_steps, n, h, w), device=dev, dtype=torch.int32)
+        dense_obs = torch.empty((n, h, w, planes), device=dev)
+    else:
+        buf_obs, dense_obs = torch.zeros((num_steps, n, h, w, planes), device=dev), None
+
+    def planes_of(o, out=None):
+        """The network's input of an obs batch: the float32 planes (packed obs: unpacked)."""
+        return packed_obs.unpack_obs(o, planes, out=out) if packed_o else o
     # the fused head reads the engine's int32 masks, and the source channel next to them
     if packed:   # the source channel is bit 0 of the packed words: no buf_src
         buf_mask = torch.zeros((num_steps, n, hw, 3), device=dev, dtype=torch.int32)
@@ -272,7 +294,10 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
     def as_dev(x):
         return (x if torch.is_tensor(x) else torch.from_numpy(np.asarray(x))).to(dev).float()
 
-    next_obs = torch.Tensor(envs.reset()).to(dev) if ref_calls else as_dev(envs.reset())   # ppo_gridnet.py:421
+    def obs_dev(o):
+        return o if packed_o else as_dev(o)
+
+    next_obs = torch.Tensor(envs.reset()).to(dev) if ref_calls else obs_dev(envs.reset())   # ppo_gridnet.py:421
     next_done = torch.zeros(n, device=dev)
     ep_ret, finished = torch.zeros(n, device=dev), []
     steps, t0, stats, stats_seen = 0, time.time(), {}, 0
@@ -293,11 +318,12 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
                     buf_mask[t], buf_src[t] = envs.get_action_mask(), envs.source_unit_mask
                 else:
                     buf_mask[t] = as_dev(envs.get_action_mask())
+                net_in = planes_of(next_obs, dense_obs)
                 if fused:
-                    a, logp, _, v = policy_fused(net, next_obs, buf_mask[t], None if packed else buf_src[t], seed=seed,
+                    a, logp, _, v = policy_fused(net, net_in, buf_mask[t], None if packed else buf_src[t], seed=seed,
                                                  step=update * num_steps + t)
                 else:
-                    a, logp, _, v = policy(net, next_obs, buf_mask[t], hw)
+                    a, logp, _, v = policy(net, net_in, buf_mask[t], hw)
             buf_act[t], buf_logp[t], buf_val[t] = a, logp, v
             if ref_calls:   # ppo_gridnet.py:475-490: host int64 actions (N, H*W*7), numpy rewards / dones, info scan
                 obs, rs, ds, infos = envs.step(a.cpu().numpy().reshape(n, -1))
@@ -310,7 +336,7 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
             else:
                 obs, rew, done, infos = envs.step(a)
                 raw = infos._raw
-                next_obs, buf_rew[t], next_done = as_dev(obs), as_dev(rew), as_dev(done)
+                next_obs, buf_rew[t], next_done = obs_dev(obs), as_dev(rew), as_dev(done)
                 ep_ret += (raw @ torch.as_tensor(envs.reward_weight, device=dev)).float()
                 if bool(next_done.any()):
                     finished += ep_ret[next_done.bool()].tolist()
@@ -322,7 +348,7 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
             first_rollout.update(obs=buf_obs.clone(), mask=buf_mask.clone(), actions=buf_act.clone(), logprob=buf_logp.clone(),
                                  source=buf_src.clone() if buf_src is not None else None)
         with torch.no_grad():   # GAE (gamma 0.99, lambda 0.95)
-            _, last_v = net(next_obs)
+            _, last_v = net(planes_of(next_obs, dense_obs))
             adv = torch.zeros_like(buf_rew)
             gae = torch.zeros(n, device=dev)
             for t in reversed(range(num_steps)):
@@ -340,6 +366,7 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
             for s in range(0, B, mb):
                 idx = perm[s:s + mb]
                 o, m, a, lp0, ad, rt, v0 = (x[idx] for x in flat)
+                o = planes_of(o)
                 ad = (ad - ad.mean()) / (ad.std() + 1e-8)
                 if fused:
                     _, lp, ent, v = policy_fused(net, o, m, None if packed else flat_src[idx], action=a)
@@ -466,7 +493,8 @@ if __name__ == "__main__":
     ap.add_argument("--max-steps", type=int, default=2000)
     ap.add_argument("--head", choices=["torch", "fused"], default="torch")
     ap.add_argument("--masks", choices=["dense", "packed"], default="dense")
+    ap.add_argument("--obs", choices=["dense", "packed"], default="dense")
     a = ap.parse_args()
     out = run(a.num_selfplay_envs, a.num_bot_envs, a.partial_obs, a.num_steps, a.updates, a.api, a.minibatches,
-              log=lambda s: print(json.dumps(s), flush=True), max_steps=a.max_steps, head=a.head, masks=a.masks)
+              log=lambda s: print(json.dumps(s), flush=True), max_steps=a.max_steps, head=a.head, masks=a.masks, obs=a.obs)
     print(json.dumps(out))

@@ -52,6 +52,7 @@ extern "C" {
 
 #define MRTS_OBS_INT32 0
 #define MRTS_OBS_FLOAT32 1
+#define MRTS_OBS_PACKED 2 /* one 32-bit one-hot word per cell: "Packed observations" below */
 
 typedef struct mrts_vec mrts_vec;
 
@@ -67,7 +68,8 @@ typedef struct {
     const char *const *map_paths;/* PhysicalGameState XML files (absolute paths)     */
     const int32_t *game_map;     /* [num_games] index into map_paths, NULL -> 0      */
     const int32_t *bot_ai;       /* [num_bot_envs] MRTS_AI_*, NULL -> passive        */
-    int32_t obs_dtype;           /* MRTS_OBS_INT32 (reference dtype) or FLOAT32      */
+    int32_t obs_dtype;           /* MRTS_OBS_INT32 (reference dtype), FLOAT32 or
+                                    PACKED (obs buffers are then [N][H][W] int32)    */
     const int32_t *bot_ai0;      /* [num_bot_envs] MRTS_AI_* of player 0 (bot vs bot,
                                     MicroRTSBotVecEnv / JNIBotClient, vec_env.py:1104-1236),
                                     -1 = the agent plays player 0; NULL = all agent */
@@ -332,6 +334,41 @@ int mrts_policy_evaluate_packed(void *stream, const float *logits, const int32_t
 int mrts_policy_evaluate_backward_packed(void *stream, const float *logits, const int32_t *packed, int32_t num_envs, int32_t hw,
                                          const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
                                          float *grad_logits);
+
+/* Packed observations: the one-hot obs as the 32-bit word per cell the engine builds
+ * it from, the form a rollout buffer can afford to keep (4 bytes a cell against the
+ * dense form's 116 or 124).
+ *   packed_obs [N][H][W] int32, holding uint32 bit patterns;
+ *   bit i of a cell's word is plane i of the dense obs of that env and cell, i < P
+ *   (P = mrts_info().obs_planes: 29, or 31 with partial obs);
+ *   bits P..31 are zero in everything this library writes, and every reader ignores
+ *   them;
+ *   a parked game's envs read the zero word, which unpacks to their all-zero dense obs.
+ * An engine created with obs_dtype = MRTS_OBS_PACKED writes these words wherever a
+ * dense engine writes obs -- mrts_reset, mrts_step, mrts_step_weighted, mrts_step_group,
+ * mrts_reset_games, mrts_park_games, mrts_load_state -- into `obs` [N][H][W] int32
+ * (16-byte stores when H * W is a multiple of 4 and `obs` is 16-byte aligned).
+ * mrts_step_group and mrts_step_group_plan refuse a group of packed and dense engines
+ * (MRTS_EINVAL, nothing stepped), and a state saved by a packed engine loads only into a
+ * packed one (the configuration fingerprint).
+ *
+ * The handle-free converters below take rows = N * H * W of any batch (up to 2^31 - 257, as the
+ * samplers do) and
+ * planes 29 or 31; the dense elements are one of MRTS_ELEM_*.  MRTS_EINVAL before any
+ * launch for a null pointer, rows out of range, any other planes or elem, or an `obs`
+ * pointer not aligned to its element size; rows == 0 is MRTS_OK and launches nothing.
+ * They run on `stream`, allocate and synchronise nothing. */
+#define MRTS_ELEM_INT32 0
+#define MRTS_ELEM_FLOAT32 1
+#define MRTS_ELEM_FLOAT16 2
+#define MRTS_ELEM_BFLOAT16 3
+/* packed [rows] -> dense [rows][planes] of 0 / 1 in `elem`; bits >= planes ignored.  Every
+ * element is written: a one as 1, 0x3f800000, 0x3c00 or 0x3f80, a zero as all-zero bits, so
+ * int32 and float32 results are an int32 / float32 engine's own obs bit for bit.  16-byte
+ * stores when `obs` is 16-byte aligned. */
+int mrts_unpack_obs(void *stream, const int32_t *packed, int64_t rows, int32_t planes, int32_t elem, void *obs);
+/* dense [rows][planes] -> packed [rows]: a bit is set where the element is non-zero (-0.0 is zero) */
+int mrts_pack_obs(void *stream, const void *obs, int64_t rows, int32_t planes, int32_t elem, int32_t *packed);
 
 /* Per-game rollout statistics, host int32 out[num_games][MRTS_GAME_STATS]:
  * game time (ticks since the game's last reset; the reference's gs.getTime()),

@@ -156,7 +156,7 @@ int cell_stride(int HW) { return HW; }
 }  // namespace
 
 struct mrts_vec {
-    int nsp = 0, nbot = 0, ngames = 0, nenvs = 0, max_steps = 0, partial_obs = 0, obs_float = 0;
+    int nsp = 0, nbot = 0, ngames = 0, nenvs = 0, max_steps = 0, partial_obs = 0, obs_kind = MRTS_OBS_INT32;
     int W = 0, H = 0, HW = 0;
     std::vector<MapData> maps;
     std::vector<std::string> map_path;   // as given to mrts_create / mrts_add_map
@@ -273,7 +273,7 @@ int mrts_create(const mrts_config *cfg, mrts_vec **out) {
     h->nenvs = h->nsp + h->nbot;
     h->max_steps = cfg->max_steps;
     h->partial_obs = cfg->partial_obs;
-    h->obs_float = cfg->obs_dtype == MRTS_OBS_FLOAT32;
+    h->obs_kind = cfg->obs_dtype == MRTS_OBS_FLOAT32 || cfg->obs_dtype == MRTS_OBS_PACKED ? cfg->obs_dtype : MRTS_OBS_INT32;
     if (cfg->map_capacity != 0 && cfg->map_capacity < cfg->num_maps)
         return fail(h, MRTS_EINVAL, "map_capacity must be 0 or >= num_maps");
     h->map_capacity = cfg->map_capacity ? cfg->map_capacity : cfg->num_maps;
@@ -385,7 +385,7 @@ int mrts_bind_workspace(mrts_vec *h, void *dev, void *stream) {
     p.nsp = h->nsp;
     p.nsp_games = h->nsp / 2;
     p.max_steps = h->max_steps;
-    p.obs_float = h->obs_float;
+    p.obs_kind = h->obs_kind;
     p.partial_obs = h->partial_obs;
     p.bot_ai = (const int32_t *)(h->ws + h->off_botai);
     p.bot_ai0 = h->nbot0 ? (const int32_t *)(h->ws + h->off_botai0) : nullptr;
@@ -536,7 +536,7 @@ static int group_plan(const EngineParams *ps, int n, int policy, int *launch_of)
     const int merge = policy & 3;
     auto lds = [&](const EngineParams &p, int NT) { return mrts_engine_step_layout(p.HW, p.W, p.fuse_bots, p.partial_obs, NT).lds_bytes; };
     auto compatible = [&](const EngineParams &a, const EngineParams &b) {
-        return a.partial_obs == b.partial_obs && a.obs_float == b.obs_float && (a.fuse_bots != 0) == (b.fuse_bots != 0);
+        return a.partial_obs == b.partial_obs && a.obs_kind == b.obs_kind && (a.fuse_bots != 0) == (b.fuse_bots != 0);
     };
     int own_nt[MRTS_STEP_GROUP_MAX];   // each member's own workgroup size, asked once
     for (int i = 0; i < n; i++) {
@@ -583,6 +583,10 @@ static int group_check(mrts_vec *const *hs, int32_t n, const mrts_step_io *io, i
             return group_fail(hs, i, MRTS_ESTATE, "step_group: workspace not bound or null buffer");
         for (int j = 0; j < i; j++)
             if (hs[j] == hs[i]) return group_fail(hs, i, MRTS_EINVAL, "step_group: an engine listed twice");
+        // int32 and float32 members only take separate launches; packed and dense obs are two formats of one
+        // batch's obs list, which no caller means
+        if ((hs[i]->obs_kind == MRTS_OBS_PACKED) != (hs[0]->obs_kind == MRTS_OBS_PACKED))
+            return group_fail(hs, i, MRTS_EINVAL, "step_group: packed and dense obs engines in one group");
     }
     return MRTS_OK;
 }
@@ -598,7 +602,7 @@ int mrts_step_group_plan(mrts_vec *const *hs, int32_t n, int32_t policy, int32_t
         ps[i].HW = hs[i]->HW;
         ps[i].W = hs[i]->W;
         ps[i].partial_obs = hs[i]->partial_obs;
-        ps[i].obs_float = hs[i]->obs_float;
+        ps[i].obs_kind = hs[i]->obs_kind;
         ps[i].fuse_bots = fused(hs[i]) ? 1 : 0;
     }
     *launches = group_plan(ps, n, policy, lo);
@@ -827,6 +831,41 @@ int mrts_unpack_masks(void *stream, const int32_t *packed, int32_t n, int32_t hw
     return mrts_engine_unpack_masks(packed, (long long)n * hw, mask, source, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
+// The obs converters (mrts_obs.hip).  Per element type: its size, a stored one's bits, and the bits that make
+// an element non-zero (a float's sign bit does not: -0.0 is zero).
+namespace {
+struct ObsElem {
+    int bytes;
+    uint32_t one, nonzero;
+};
+bool obs_elem(int32_t elem, ObsElem *e) {
+    switch (elem) {
+    case MRTS_ELEM_INT32: *e = {4, 1u, 0xffffffffu}; return true;
+    case MRTS_ELEM_FLOAT32: *e = {4, 0x3f800000u, 0x7fffffffu}; return true;
+    case MRTS_ELEM_FLOAT16: *e = {2, 0x3c00u, 0x7fffu}; return true;
+    case MRTS_ELEM_BFLOAT16: *e = {2, 0x3f80u, 0x7fffu}; return true;
+    }
+    return false;
+}
+bool obs_args_ok(const void *packed, const void *obs, int64_t rows, int32_t planes, int32_t elem, ObsElem *e) {
+    // (the samplers' row bound, 2^31 - 257: a grid below 2^23 workgroups of 256 rows)
+    return packed && obs && rows >= 0 && rows <= 2147483391ll && (planes == 29 || planes == 31) && obs_elem(elem, e) &&
+           ((uintptr_t)obs & (uintptr_t)(e->bytes - 1)) == 0 && ((uintptr_t)packed & 3u) == 0;
+}
+}  // namespace
+
+int mrts_unpack_obs(void *stream, const int32_t *packed, int64_t rows, int32_t planes, int32_t elem, void *obs) {
+    ObsElem e;
+    if (!obs_args_ok(packed, obs, rows, planes, elem, &e)) return MRTS_EINVAL;
+    return mrts_engine_unpack_obs(packed, rows, planes, e.bytes, e.one, obs, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
+int mrts_pack_obs(void *stream, const void *obs, int64_t rows, int32_t planes, int32_t elem, int32_t *packed) {
+    ObsElem e;
+    if (!obs_args_ok(packed, obs, rows, planes, elem, &e)) return MRTS_EINVAL;
+    return mrts_engine_pack_obs(obs, rows, planes, e.bytes, e.nonzero, packed, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
 int mrts_bind_mask_outputs(mrts_vec *h, int32_t *mask, int32_t *source) {
     if (!bound(h)) return fail(h, MRTS_ESTATE, "bind_mask_outputs: workspace not bound");
     if ((mask == nullptr) != (source == nullptr)) return fail(h, MRTS_EINVAL, "bind_mask_outputs: mask and source go together");
@@ -878,7 +917,7 @@ struct Fnv {
 // the caller may reassign those between steps (vec_env.py reads reward_weight every step).
 uint64_t config_fingerprint(const mrts_vec *h) {
     Fnv f;
-    for (int32_t x : {h->nsp, h->nbot, h->partial_obs, h->obs_float, h->game_offset, h->map_capacity, h->W, h->H,
+    for (int32_t x : {h->nsp, h->nbot, h->partial_obs, h->obs_kind, h->game_offset, h->map_capacity, h->W, h->H,
                       h->max_steps})
         f.i32(x);
     f.i32((int32_t)h->bot_ai.size());

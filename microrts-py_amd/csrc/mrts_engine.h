@@ -1,7 +1,7 @@
 // mrts_engine.h -- internal launch interface between the C ABI (mrts_capi.cpp)
 // and the kernels: the game step, output streams and renderer (mrts_engine.hip),
-// the scripted opponents (mrts_bots.hip), the stand-in samplers (mrts_sampler.hip)
-// and the masked action head (mrts_policy.hip).
+// the scripted opponents (mrts_bots.hip), the stand-in samplers (mrts_sampler.hip),
+// the masked action head (mrts_policy.hip) and the obs converters (mrts_obs.hip).
 #ifndef MRTS_ENGINE_H
 #define MRTS_ENGINE_H
 #include <hip/hip_runtime.h>
@@ -103,10 +103,12 @@ struct EngineParams {
     const int32_t *map_scal;// [maps][MRTS_MAP_SCALARS]
     int G, HW, W, H;
     int nmaps;              // map templates (1: every game's terrain is map 0's)
-    int nsp, nsp_games, max_steps, obs_float, partial_obs;
+    int nsp, nsp_games, max_steps;
+    int obs_kind;           // MRTS_OBS_*: what `obs` holds (the kernels' OT: int32_t, float, or mrts::PackedObs)
+    int partial_obs;
     const int64_t *actions; // [N][HW][7]
     const int32_t *src;     // [N][HW]
-    void *obs;              // [N][HW][P]
+    void *obs;              // [N][HW][P], or the packed words [N][HW] (MRTS_OBS_PACKED)
     double *raw_reward;     // [N][6]
     uint8_t *done;          // [N][6]
     int32_t *mask;          // [N][HW][78]: k_masks output; k_step / k_reset write the
@@ -180,6 +182,10 @@ hipError_t mrts_engine_policy_eval_bwd(int packed, const float *logits, const in
                                        const int64_t *act, const float *g_lp, const float *g_ent, float *grad, hipStream_t s);
 hipError_t mrts_engine_pack_masks(const int32_t *mask, const int32_t *src, long long rows, int32_t *packed, hipStream_t s);
 hipError_t mrts_engine_unpack_masks(const int32_t *packed, long long rows, int32_t *mask, int32_t *src, hipStream_t s);
+// mrts_obs.hip: the converters between the packed obs words (mrts_rules.h cell_onehot) and the dense planes.
+// elem_bytes 2 or 4; `one`: a stored one's bits (unpack); `nonzero`: the bits that make an element non-zero (pack)
+hipError_t mrts_engine_unpack_obs(const int32_t *packed, long long rows, int planes, int elem_bytes, uint32_t one, void *obs, hipStream_t s);
+hipError_t mrts_engine_pack_obs(const void *obs, long long rows, int planes, int elem_bytes, uint32_t nonzero, int32_t *packed, hipStream_t s);
 // mrts_engine.hip again (mrts_engine_bot_lds_bytes: mrts_bots.hip)
 hipError_t mrts_engine_masks_packed(const EngineParams *p, hipStream_t s, int32_t *packed);
 hipError_t mrts_engine_render(const EngineParams *p, hipStream_t s, int game, int map, int size, uint8_t *rgb);

@@ -454,6 +454,31 @@ __device__ __forceinline__ void stream_obs(const EngineParams& p, const Lds& L, 
         for (int e = t0; e < total; e += nt) out[e] = (OT)((ow[e / P] >> (e % P)) & 1u);
     }
 }
+// Packed obs (MRTS_OBS_PACKED, OT = PackedObs; the format: mrts_rules.h cell_onehot): phase B's
+// obs are the views' NV * HW one-hot words as phase A left them, copied out to p.obs [N][HW].
+// HW % 4 == 0: every game's run starts 16-B aligned in a 16-B aligned buffer, in LDS too (outw
+// is a carved array), so 16-byte copies; otherwise (9x13, or a buffer off 16 B) per word.
+// Reads nothing but outw and kernel parameters, as phase B must.
+struct PackedObs {};
+template <typename OT>
+constexpr bool obs_packed = std::is_same<OT, PackedObs>::value;
+__device__ __forceinline__ void stream_obs_words(const EngineParams& p, const Lds& L, const Game& G, int t0, int nt) {
+    const int HW = p.HW, n = G.nviews * HW;
+    const uint32_t* ow = L.outw;
+    int32_t* out = reinterpret_cast<int32_t*>(p.obs) + (size_t)G.env0 * HW;
+    if ((HW & 3) == 0 && ((uintptr_t)p.obs & 15u) == 0) {
+        const v4i* w4 = reinterpret_cast<const v4i*>(ow);
+        for (int k = t0; k < n / 4; k += nt) *reinterpret_cast<v4i*>(out + 4 * k) = w4[k];
+    } else {
+        for (int i = t0; i < n; i += nt) out[i] = (int32_t)ow[i];
+    }
+}
+// phase B's obs of every view in the engine's obs kind
+template <int P, typename OT>
+__device__ __forceinline__ void stream_obs_kind(const EngineParams& p, const Lds& L, const Game& G, int t0, int nt) {
+    if constexpr (obs_packed<OT>) stream_obs_words(p, L, G, t0, nt);
+    else stream_obs<P, OT>(p, L, G, t0, nt);
+}
 // phase B's mask rows of every view, lanes t0 .. t0 + nt
 __device__ __forceinline__ void stream_masks(const EngineParams& p, const Lds& L, const Game& G, int t0, int nt) {
     const int HW = p.HW, NV = G.nviews;
@@ -572,7 +597,7 @@ __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L
         }
         for (int c = threadIdx.x; c < HW; c += NT) onehot_words<P>(p, L, G, c);
         __syncthreads();
-        stream_obs<P, OT>(p, L, G, threadIdx.x, NT);
+        stream_obs_kind<P, OT>(p, L, G, threadIdx.x, NT);
         MRTS_STAMP_MAX(9, (threadIdx.x & 63) == 0);
         return;
     }
@@ -601,7 +626,7 @@ __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L
     MRTS_STAMP(8, (int)threadIdx.x == skip);
     __builtin_amdgcn_s_setprio(0);
     const int t0 = (int)threadIdx.x - skip, nt = NT - skip;
-    if (obs) stream_obs<P, OT>(p, L, G, t0, nt);
+    if (obs) stream_obs_kind<P, OT>(p, L, G, t0, nt);
     if (masks && delta) stream_masks_delta(p, L, G, t0, nt);
     else if (masks) stream_masks(p, L, G, t0, nt);
     MRTS_STAMP_MAX(9, (threadIdx.x & 63) == 0);
@@ -620,8 +645,13 @@ __device__ __forceinline__ void zero_mask_rows(const EngineParams& p, const Game
 template <int NT, int P, typename OT>
 __device__ __forceinline__ void zero_outputs(const EngineParams& p, const Game& G) {
     const size_t n = (size_t)G.nviews * p.HW;
-    OT* obs = reinterpret_cast<OT*>(p.obs) + (size_t)G.env0 * p.HW * P;
-    for (size_t i = threadIdx.x; i < n * P; i += NT) obs[i] = (OT)0;
+    if constexpr (obs_packed<OT>) {   // the zero word: what unpacks to the dense zeros
+        int32_t* obs = reinterpret_cast<int32_t*>(p.obs) + (size_t)G.env0 * p.HW;
+        for (size_t i = threadIdx.x; i < n; i += NT) obs[i] = 0;
+    } else {
+        OT* obs = reinterpret_cast<OT*>(p.obs) + (size_t)G.env0 * p.HW * P;
+        for (size_t i = threadIdx.x; i < n * P; i += NT) obs[i] = (OT)0;
+    }
     zero_mask_rows<NT>(p, G);
 }
 
@@ -1644,17 +1674,17 @@ static auto with_nt(int NT, F&& f) {
     return NT == 64 ? f(ic<64>{}) : NT == 128 ? f(ic<128>{}) : f(ic<256>{});
 }
 template <typename F>
-static auto with_obs(bool partial, bool fl, F&& f) {
-    if (partial) return fl ? f(ic<31>{}, float{}) : f(ic<31>{}, int32_t{});
-    return fl ? f(ic<29>{}, float{}) : f(ic<29>{}, int32_t{});
+static auto with_obs(bool partial, int kind, F&& f) {
+    auto planes = [&](auto ot) { return partial ? f(ic<31>{}, ot) : f(ic<29>{}, ot); };
+    return kind == MRTS_OBS_PACKED ? planes(PackedObs{}) : kind == MRTS_OBS_FLOAT32 ? planes(float{}) : planes(int32_t{});
 }
 
 // The step kernel of a launch's (planes, obs type, bot fusion).  No 64-lane launch
 // is fused (step_nt: the fused step needs a wave besides the bot's), so no fused
 // 64-lane kernel is built.
 template <int NT>
-static void launch_step(const StepGroup& sg, int grid, size_t sh, hipStream_t s, bool partial, bool fl, bool fb) {
-    with_obs(partial, fl, [&](auto planes, auto ot) {
+static void launch_step(const StepGroup& sg, int grid, size_t sh, hipStream_t s, bool partial, int kind, bool fb) {
+    with_obs(partial, kind, [&](auto planes, auto ot) {
         constexpr int P = decltype(planes)::value;
         using OT = decltype(ot);
         if (!fb) hipLaunchKernelGGL((k_step<NT, P, OT>), dim3(grid), dim3(NT), sh, s, sg);
@@ -1688,7 +1718,7 @@ static hipError_t step_group(const EngineParams* ps, int n, hipStream_t s, bool 
     int NT = 64;
     for (int i = 0; i < n; i++) {
         const EngineParams& p = ps[i];
-        if (p.partial_obs != p0.partial_obs || p.obs_float != p0.obs_float || (p.fuse_bots != 0) != fused) return hipErrorInvalidValue;
+        if (p.partial_obs != p0.partial_obs || p.obs_kind != p0.obs_kind || (p.fuse_bots != 0) != fused) return hipErrorInvalidValue;
         NT = std::max(NT, step_nt(p.HW, fused));
     }
     StepGroup sg{};
@@ -1719,7 +1749,7 @@ static hipError_t step_group(const EngineParams* ps, int n, hipStream_t s, bool 
         }
     sg.seg_block[sg.nseg] = grid;
     if (grid == 0) return hipSuccess;
-    with_nt(NT, [&](auto nt) { launch_step<decltype(nt)::value>(sg, grid, sh, s, p0.partial_obs, p0.obs_float, fused); });
+    with_nt(NT, [&](auto nt) { launch_step<decltype(nt)::value>(sg, grid, sh, s, p0.partial_obs, p0.obs_kind, fused); });
     return hipGetLastError();
 }
 
@@ -1744,13 +1774,13 @@ int mrts_debug_stamps(unsigned long long* out, int max_rows, int reset) {
 }
 #endif
 hipError_t mrts_engine_reset(const EngineParams* p, hipStream_t s, const int32_t* games, const int32_t* maps, int count) {
-    return mrts::with_obs(p->partial_obs, p->obs_float, [&](auto planes, auto ot) {
+    return mrts::with_obs(p->partial_obs, p->obs_kind, [&](auto planes, auto ot) {
         auto k = [](auto nt) { return mrts::k_reset<decltype(nt)::value, decltype(planes)::value, decltype(ot)>; };
         return mrts::per_game(*p, games ? count : p->G, s, k, games, maps, count);
     });
 }
 hipError_t mrts_engine_outputs(const EngineParams* p, hipStream_t s) {
-    return mrts::with_obs(p->partial_obs, p->obs_float, [&](auto planes, auto ot) {
+    return mrts::with_obs(p->partial_obs, p->obs_kind, [&](auto planes, auto ot) {
         return mrts::per_game(*p, p->G, s, [](auto nt) { return mrts::k_outputs<decltype(nt)::value, decltype(planes)::value, decltype(ot)>; });
     });
 }

@@ -227,6 +227,10 @@ __device__ inline void cell_mask(const Grid& gd, int c, int player, const uint32
 // Partial observability (P == 31, PartiallyObservableGameState): `shown` is 0
 // for a unit the player cannot see (the cell reads as empty); bits 29/30 are
 // the visibility plane: the shown unit is visible to the opponent.
+// The word is also the packed obs (MRTS_OBS_PACKED, include/microrts_amd.h "Packed
+// observations"), written out as it is: bit i = plane i of the dense obs for i < P,
+// plane groups of 5 (hp) 5 (resources) 3 (owner) 8 (type) 6 (action) 2 (terrain) and,
+// P == 31, 2 (visibility) bits with exactly one bit set in each; no bit at or above P.
 __device__ __forceinline__ uint32_t cell_onehot(uint32_t u, uint32_t a, uint8_t wall, int player, int P = 29,
                                                 bool shown = true, bool opp_sees = false) {
     uint32_t b = 0;

@@ -15,6 +15,8 @@ LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libmicrorts
 MRTS_OK = 0
 MRTS_OBS_INT32 = 0
 MRTS_OBS_FLOAT32 = 1
+MRTS_OBS_PACKED = 2
+MRTS_ELEM_INT32, MRTS_ELEM_FLOAT32, MRTS_ELEM_FLOAT16, MRTS_ELEM_BFLOAT16 = 0, 1, 2, 3
 MRTS_GAME_STATS = 6
 ERROR_NAMES = {-1: "EINVAL", -2: "EIO", -3: "EHIP", -4: "ENOTIMPL", -5: "ESTATE"}
 
@@ -111,6 +113,8 @@ SIGNATURES = {
     "mrts_get_masks_packed": (ctypes.c_int, [P, P, P]),
     "mrts_pack_masks": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, P]),
     "mrts_unpack_masks": (ctypes.c_int, [P, P, ctypes.c_int32, ctypes.c_int32, P, P]),
+    "mrts_unpack_obs": (ctypes.c_int, [P, P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, P]),
+    "mrts_pack_obs": (ctypes.c_int, [P, P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, P]),
     "mrts_policy_sample_packed": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
                                                  ctypes.c_uint32, P, P, P]),
     "mrts_policy_evaluate_packed": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P]),

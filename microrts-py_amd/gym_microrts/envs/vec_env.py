@@ -203,10 +203,19 @@ class MicroRTSGridModeVecEnv:
         bot_fusion=True,
         mask_delta=None,
         game_offset=0,
+        obs_format="dense",
         _ai1s=None,
         _extra_maps=(),
     ):
-        """mask_delta (eager masks only; None = on, unless the environment variable
+        """obs_format: "dense" -- obs are [N, H, W, P] one-hot planes in obs_dtype -- or
+        "packed": the engine writes the 32-bit one-hot word per cell it builds the planes
+        from (bit i = plane i; include/microrts_amd.h "Packed observations"), obs are
+        [N, H, W] int32 (a device tensor on the tensor and hybrid contracts, a numpy array
+        on the numpy contract) and obs_dtype must be None or torch.int32.
+        observation_space describes the dense obs either way;
+        gym_microrts.packed_obs.unpack_obs turns the words into planes.
+
+        mask_delta (eager masks only; None = on, unless the environment variable
         MICRORTS_AMD_MASK_DELTA=0): step() stores only the mask rows that can differ
         from the last tick's -- the source cells before and after the tick -- instead of
         all N * H*W of them (mrts_set_mask_delta).  The tensor get_action_mask() returns
@@ -279,16 +288,25 @@ class MicroRTSGridModeVecEnv:
         self.contract = contract_of(return_tensors)
         self.return_tensors = self.contract == "tensors"
         self._host_outputs = self.contract == "numpy"   # obs / masks copied to numpy
+        if obs_format not in ("dense", "packed"):
+            raise ValueError(f"obs_format must be 'dense' or 'packed', not {obs_format!r}")
+        self.obs_format = obs_format
+        packed_obs = obs_format == "packed"
+        if packed_obs:
+            if obs_dtype not in (None, torch.int32):
+                raise ValueError("obs_format='packed' holds int32 words: obs_dtype must be None or torch.int32")
+            obs_dtype = torch.int32
         if obs_dtype is None:
             obs_dtype = torch.int32 if self._host_outputs else torch.float32
         if obs_dtype not in (torch.float32, torch.int32):
             raise ValueError("obs_dtype must be torch.float32 or torch.int32")
         self.obs_dtype = obs_dtype
+        obs_kind = (_native.MRTS_OBS_PACKED if packed_obs else
+                    _native.MRTS_OBS_FLOAT32 if obs_dtype == torch.float32 else _native.MRTS_OBS_INT32)
 
         # new JNIGridnetVecClient(...) (vec_env.py:256-276)
         self._h = _native.create(num_selfplay_envs, num_bot_envs, max_steps, partial_obs, self._map_table, game_map,
-                                 bot_ai, _native.MRTS_OBS_FLOAT32 if obs_dtype == torch.float32 else _native.MRTS_OBS_INT32,
-                                 bot_ai0=bot_ai0, game_offset=game_offset)
+                                 bot_ai, obs_kind, bot_ai0=bot_ai0, game_offset=game_offset)
         self._game_map = list(game_map)
         info = _native.info(self._h)
         assert (info.height, info.width) == (self.height, self.width)
@@ -304,7 +322,8 @@ class MicroRTSGridModeVecEnv:
             if partial_obs:
                 self.num_planes = [5, 5, 3, len(self.utt["unitTypes"]) + 1, 6, 2, 2]
             P = sum(self.num_planes)
-            self._obs = torch.empty((self.num_envs, self.height, self.width, P), dtype=obs_dtype, device=self.device)
+            obs_shape = (self.num_envs, self.height, self.width) + (() if packed_obs else (P,))
+            self._obs = torch.empty(obs_shape, dtype=obs_dtype, device=self.device)
             self._mask = torch.zeros((self.num_envs, hw, 78), dtype=torch.int32, device=self.device)
             self._src = torch.zeros((self.num_envs, hw), dtype=torch.int32, device=self.device)
             self._raw = torch.zeros((self.num_envs, 6), dtype=torch.float64, device=self.device)
@@ -896,7 +915,7 @@ class MicroRTSMixedMapVecEnv:
       mask = env.get_action_mask()             # list over buckets
       obs, rew, done, infos = env.step(actions)  # actions: list over buckets
 
-    Keyword arguments (mask_delta among them) go to every bucket's engine.
+    Keyword arguments (mask_delta and obs_format among them) go to every bucket's engine.
     """
 
     def __init__(self, buckets, concurrent=False, group_policy="default", **common):
@@ -1041,8 +1060,9 @@ class MicroRTSSizeCyclingVecEnv:
 
     def __init__(self, num_selfplay_envs, num_bot_envs, ai2s=[], map_paths=["maps/16x16/basesWorkers16x16.xml"], cycle_maps=[],
                  max_steps=2000, partial_obs=False, reward_weight=np.array([0.0, 1.0, 0.0, 0.0, 0.0, 5.0]), device=None,
-                 obs_dtype=None, mask_delta=None):
+                 obs_dtype=None, mask_delta=None, obs_format="dense"):
         self.num_selfplay_envs, self.num_bot_envs = num_selfplay_envs, num_bot_envs
+        self.obs_format = obs_format   # every size engine's (MicroRTSGridModeVecEnv: obs entries [N, H_i, W_i] int32 when "packed")
         self.num_envs = num_selfplay_envs + num_bot_envs
         root = os.path.join(gym_microrts.__path__[0], "microrts")
         per_env = list(map_paths) * self.num_envs if len(map_paths) == 1 else list(map_paths)
@@ -1064,7 +1084,7 @@ class MicroRTSSizeCyclingVecEnv:
             self.envs.append(MicroRTSGridModeVecEnv(num_selfplay_envs, num_bot_envs, partial_obs=partial_obs, max_steps=max_steps,
                                                     ai2s=ai2s, map_paths=maps_i, reward_weight=reward_weight, device=device,
                                                     return_tensors=True, obs_dtype=obs_dtype, mask_delta=mask_delta,
-                                                    _extra_maps=own))
+                                                    obs_format=obs_format, _extra_maps=own))
         self.device = self.envs[0].device
         self.reward_weight = reward_weight
 
