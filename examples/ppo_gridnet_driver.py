@@ -22,6 +22,8 @@ envs) runs end to end on the GPU.
   --obs packed : the engine writes one 32-bit one-hot word per cell (obs_format="packed") and the
                  rollout buffer keeps those -- 4 bytes a cell against 116 / 124 -- unpacking
                  them (gym_microrts.packed_obs) for each forward; --api tensor only
+  --encoder fused : with --obs packed, the network's first stage (conv3x3 + max-pool + ReLU) reads
+                 the words themselves (gym_microrts.obs_conv): no forward unpacks anything
 
   --head fused : gym_microrts.policy_head -- the head as HIP kernels that read only the
                  rows of cells holding a unit that can act (sample in the rollout,
@@ -55,7 +57,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "microrts-py_amd"))
 
-from gym_microrts import microrts_ai, packed_obs, policy_head  # noqa: E402
+from gym_microrts import microrts_ai, obs_conv, packed_obs, policy_head  # noqa: E402
 from gym_microrts.envs.vec_env import MicroRTSGridModeVecEnv  # noqa: E402
 from gym_microrts.run_driver import install as _install_compat  # noqa: E402
 
@@ -123,7 +125,12 @@ class GridNet(nn.Module):
         return done
 
     def forward(self, obs):
-        z = self.enc(obs.permute(0, 3, 1, 2))
+        """obs: the float planes [N, H, W, P], or the packed obs words [N, H, W] int32, which
+        the first stage then reads directly (obs_conv.encode with enc.0's parameters)."""
+        if obs.dtype == torch.int32 and obs.dim() == 3:
+            z = self.enc[3:](obs_conv.encode(obs, self.enc[0].weight, self.enc[0].bias))
+        else:
+            z = self.enc(obs.permute(0, 3, 1, 2))
         logits = self.pi(z).permute(0, 2, 3, 1).reshape(obs.shape[0] * self.hw, sum(NVEC))
         return logits, self.v(z).squeeze(-1)
 
@@ -222,7 +229,7 @@ def bot_list(n):
 
 def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, updates=2, api="numpy", minibatches=4,
         epochs=2, seed=1, device="cuda", log=print, max_steps=2000, head="torch", keep_first_rollout=False, masks="dense",
-        obs="dense"):
+        obs="dense", encoder="torch"):
     """head: "torch" or "fused" (policy_fused; --api tensor only).  keep_first_rollout: the
     returned stats carry "first_rollout" -- the first rollout's buffers and the weights
     that acted in it.  masks: "dense", or "packed" (--head fused only): the rollout buffer
@@ -230,7 +237,8 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
     source, and the update gathers and evaluates from them.  obs: "dense", or "packed"
     (--api tensor only): the engine writes the packed obs words, the buffer holds them
     ([T, N, H, W] int32) and every forward reads packed_obs.unpack_obs of them -- the same
-    float32 planes the dense run sees."""
+    float32 planes the dense run sees.  encoder: "torch", or "fused" (--obs packed only): the
+    network takes the words and its first stage is obs_conv.encode, so nothing is unpacked."""
     if head not in ("torch", "fused"):
         raise ValueError(f"head must be 'torch' or 'fused', not {head!r}")
     if head == "fused" and api != "tensor":
@@ -243,7 +251,12 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
         raise ValueError(f"obs must be 'dense' or 'packed', not {obs!r}")
     if obs == "packed" and api != "tensor":
         raise ValueError("--obs packed needs --api tensor: the packed words are unpacked on the device")
+    if encoder not in ("torch", "fused"):
+        raise ValueError(f"encoder must be 'torch' or 'fused', not {encoder!r}")
+    if encoder == "fused" and obs != "packed":
+        raise ValueError("--encoder fused needs --obs packed: the fused first stage reads the packed words")
     packed_o = obs == "packed"
+    fused_enc = encoder == "fused"
     fused = head == "fused"
     packed = masks == "packed"
     torch.manual_seed(seed)
@@ -275,13 +288,14 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
     opt = torch.optim.Adam(net.parameters(), lr=2.5e-4, eps=1e-5)
     if packed_o:   # the words; `dense_obs` is the one dense tensor the rollout's forwards unpack into
         buf_obs = torch.zeros((num_steps, n, h, w), device=dev, dtype=torch.int32)
-        dense_obs = torch.empty((n, h, w, planes), device=dev)
+        dense_obs = None if fused_enc else torch.empty((n, h, w, planes), device=dev)
     else:
         buf_obs, dense_obs = torch.zeros((num_steps, n, h, w, planes), device=dev), None
 
     def planes_of(o, out=None):
-        """The network's input of an obs batch: the float32 planes (packed obs: unpacked)."""
-        return packed_obs.unpack_obs(o, planes, out=out) if packed_o else o
+        """The network's input of an obs batch: the float32 planes (packed obs: unpacked), or the
+        words themselves for the fused first stage."""
+        return packed_obs.unpack_obs(o, planes, out=out) if packed_o and not fused_enc else o
     # the fused head reads the engine's int32 masks, and the source channel next to them
     if packed:   # the source channel is bit 0 of the packed words: no buf_src
         buf_mask = torch.zeros((num_steps, n, hw, 3), device=dev, dtype=torch.int32)
@@ -385,7 +399,8 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
         stats = {"update": update + 1, "global_step": steps, "sps": round(steps / (time.time() - t0), 1),
                  "rollout_env_steps_per_s": round(steps / rollout_s, 1), "loss": float(loss.detach()), "policy_loss": float(pg.detach()),
                  "value_loss": float(vl.detach()), "entropy": float(ent.detach().mean()), "episodes": len(finished),
-                 "microrts_stats_infos": stats_seen, "api": api, "num_envs": n, "partial_obs": bool(partial_obs), "head": head}
+                 "microrts_stats_infos": stats_seen, "api": api, "num_envs": n, "partial_obs": bool(partial_obs), "head": head,
+                 "encoder": encoder}
         log(stats)
     stats["engine_error_flags"] = base.error_flags()
     stats["finite"] = bool(np.isfinite([stats["loss"], stats["value_loss"], stats["entropy"]]).all())
@@ -494,7 +509,9 @@ if __name__ == "__main__":
     ap.add_argument("--head", choices=["torch", "fused"], default="torch")
     ap.add_argument("--masks", choices=["dense", "packed"], default="dense")
     ap.add_argument("--obs", choices=["dense", "packed"], default="dense")
+    ap.add_argument("--encoder", choices=["torch", "fused"], default="torch")
     a = ap.parse_args()
     out = run(a.num_selfplay_envs, a.num_bot_envs, a.partial_obs, a.num_steps, a.updates, a.api, a.minibatches,
-              log=lambda s: print(json.dumps(s), flush=True), max_steps=a.max_steps, head=a.head, masks=a.masks, obs=a.obs)
+              log=lambda s: print(json.dumps(s), flush=True), max_steps=a.max_steps, head=a.head, masks=a.masks, obs=a.obs,
+              encoder=a.encoder)
     print(json.dumps(out))

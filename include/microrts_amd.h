@@ -370,6 +370,37 @@ int mrts_unpack_obs(void *stream, const int32_t *packed, int64_t rows, int32_t p
 /* dense [rows][planes] -> packed [rows]: a bit is set where the element is non-zero (-0.0 is zero) */
 int mrts_pack_obs(void *stream, const void *obs, int64_t rows, int32_t planes, int32_t elem, int32_t *packed);
 
+/* The first encoder stage of a GridNet policy on the packed words, with no dense obs in between:
+ * Conv2d(planes, channels, 3, padding = 1) -> MaxPool2d(3, 2, 1) -> ReLU.
+ *   packed [n][height][width] int32 (bits >= planes ignored), weight [channels][planes][3][3]
+ *   float32 (nn.Conv2d.weight's layout), bias [channels] float32;
+ *   out [n][channels][Ho][Wo] float32, Ho = (height - 1) / 2 + 1, Wo = (width - 1) / 2 + 1.
+ * Defined for arbitrary words.  conv(n, c, y, x) starts from bias[c] and visits the taps (ky, kx),
+ * 0..2 each in row-major order, neighbour (y + ky - 1, x + kx - 1): a neighbour outside the map or
+ * with a zero word (a parked game's) is skipped; otherwise t = the sum of weight[c][p][ky][kx]
+ * over the word's set bits p in ascending order, starting from the first one's weight, and then
+ * acc = acc + t.  Every + is one float32 round-to-nearest add, none reassociated.  A pooled
+ * output is the first maximum (strict >) of conv over rows 2 i - 1 .. 2 i + 1 and columns
+ * 2 j - 1 .. 2 j + 1 in row-major order, positions outside the map left out; out is that
+ * maximum m when m > 0, else +0.0.  NaN or infinite weights are outside the contract.
+ * The backward overwrites grad_weight [channels][planes][3][3] and grad_bias [channels]
+ * from grad_out [n][channels][Ho][Wo]: for every output with m > 0, whose first maximum is at
+ * (y, x), g = grad_out's element is added to grad_bias[c] and to grad_weight[c][p][ky][kx] for
+ * every tap whose neighbour is inside the map and has bit p set.  It recomputes the forward from
+ * the words, sums in a fixed order (no float atomics: the same inputs give the same bits), and
+ * needs a `workspace` of at least the queried size, 16-byte aligned, whose contents it
+ * overwrites.  The query returns that size in bytes (0 for n == 0), or MRTS_EINVAL.
+ * MRTS_EINVAL before any launch for a null pointer, planes other than 29 or 31, channels outside
+ * 1..64, height or width below 1, a map of more than 4096 cells, n < 0 or n * height * width
+ * above 2^31 - 257, or a workspace smaller than the query's; n == 0 is MRTS_OK and launches
+ * nothing (the gradients are then left as they are).  They run on `stream`, allocate and synchronise nothing. */
+int64_t mrts_obs_conv_workspace_bytes(int32_t n, int32_t height, int32_t width, int32_t planes, int32_t channels);
+int mrts_obs_conv_forward(void *stream, const int32_t *packed, int32_t n, int32_t height, int32_t width, int32_t planes,
+                          const float *weight, const float *bias, int32_t channels, float *out);
+int mrts_obs_conv_backward(void *stream, const int32_t *packed, int32_t n, int32_t height, int32_t width, int32_t planes,
+                           const float *weight, const float *bias, int32_t channels, const float *grad_out,
+                           void *workspace, int64_t workspace_bytes, float *grad_weight, float *grad_bias);
+
 /* Per-game rollout statistics, host int32 out[num_games][MRTS_GAME_STATS]:
  * game time (ticks since the game's last reset; the reference's gs.getTime()),
  * env steps of the episode, steps since creation, and three never-reset

@@ -866,6 +866,37 @@ int mrts_pack_obs(void *stream, const void *obs, int64_t rows, int32_t planes, i
     return mrts_engine_pack_obs(obs, rows, planes, e.bytes, e.nonzero, packed, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
+// The first encoder stage on the packed words (mrts_conv.hip): one shape check for the query and both launches.
+static bool obs_conv_shape_ok(int32_t n, int32_t height, int32_t width, int32_t planes, int32_t channels) {
+    return n >= 0 && height >= 1 && width >= 1 && (int64_t)height * width <= MRTS_MAX_HW && (planes == 29 || planes == 31) &&
+           channels >= 1 && channels <= 64 && (int64_t)n * height * width <= 2147483391ll;
+}
+
+int64_t mrts_obs_conv_workspace_bytes(int32_t n, int32_t height, int32_t width, int32_t planes, int32_t channels) {
+    if (!obs_conv_shape_ok(n, height, width, planes, channels)) return MRTS_EINVAL;
+    const long long b = mrts_engine_obs_conv_workspace(n, height, width, planes, channels);
+    return b < 0 ? MRTS_EINVAL : b;
+}
+
+int mrts_obs_conv_forward(void *stream, const int32_t *packed, int32_t n, int32_t height, int32_t width, int32_t planes,
+                          const float *weight, const float *bias, int32_t channels, float *out) {
+    if (!packed || !weight || !bias || !out || mrts_obs_conv_workspace_bytes(n, height, width, planes, channels) < 0) return MRTS_EINVAL;
+    if (n == 0) return MRTS_OK;
+    return mrts_engine_obs_conv_fwd(packed, n, height, width, planes, weight, bias, channels, out, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
+int mrts_obs_conv_backward(void *stream, const int32_t *packed, int32_t n, int32_t height, int32_t width, int32_t planes,
+                           const float *weight, const float *bias, int32_t channels, const float *grad_out,
+                           void *workspace, int64_t workspace_bytes, float *grad_weight, float *grad_bias) {
+    const int64_t need = mrts_obs_conv_workspace_bytes(n, height, width, planes, channels);
+    if (!packed || !weight || !bias || !grad_out || !workspace || !grad_weight || !grad_bias || need < 0 || workspace_bytes < need ||
+        !aligned16(workspace))
+        return MRTS_EINVAL;
+    if (n == 0) return MRTS_OK;
+    return mrts_engine_obs_conv_bwd(packed, n, height, width, planes, weight, bias, channels, grad_out, (float *)workspace, grad_weight,
+                                    grad_bias, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
 int mrts_bind_mask_outputs(mrts_vec *h, int32_t *mask, int32_t *source) {
     if (!bound(h)) return fail(h, MRTS_ESTATE, "bind_mask_outputs: workspace not bound");
     if ((mask == nullptr) != (source == nullptr)) return fail(h, MRTS_EINVAL, "bind_mask_outputs: mask and source go together");

@@ -1,7 +1,8 @@
 // mrts_engine.h -- internal launch interface between the C ABI (mrts_capi.cpp)
 // and the kernels: the game step, output streams and renderer (mrts_engine.hip),
 // the scripted opponents (mrts_bots.hip), the stand-in samplers (mrts_sampler.hip),
-// the masked action head (mrts_policy.hip) and the obs converters (mrts_obs.hip).
+// the masked action head (mrts_policy.hip), the obs converters (mrts_obs.hip) and
+// the first encoder stage on the packed obs (mrts_conv.hip).
 #ifndef MRTS_ENGINE_H
 #define MRTS_ENGINE_H
 #include <hip/hip_runtime.h>
@@ -186,6 +187,13 @@ hipError_t mrts_engine_unpack_masks(const int32_t *packed, long long rows, int32
 // elem_bytes 2 or 4; `one`: a stored one's bits (unpack); `nonzero`: the bits that make an element non-zero (pack)
 hipError_t mrts_engine_unpack_obs(const int32_t *packed, long long rows, int planes, int elem_bytes, uint32_t one, void *obs, hipStream_t s);
 hipError_t mrts_engine_pack_obs(const void *obs, long long rows, int planes, int elem_bytes, uint32_t nonzero, int32_t *packed, hipStream_t s);
+// mrts_conv.hip: the first encoder stage on the packed words (conv3x3 + max-pool + ReLU), its backward to the
+// parameters (k_obs_conv_bwd into `ws`, then the reduction) and the bytes `ws` needs (-1: no tile of the shape fits)
+long long mrts_engine_obs_conv_workspace(int n, int h, int w, int planes, int channels);
+hipError_t mrts_engine_obs_conv_fwd(const int32_t *packed, int n, int h, int w, int planes, const float *weight, const float *bias,
+                                    int channels, float *out, hipStream_t s);
+hipError_t mrts_engine_obs_conv_bwd(const int32_t *packed, int n, int h, int w, int planes, const float *weight, const float *bias,
+                                    int channels, const float *grad_out, float *ws, float *grad_weight, float *grad_bias, hipStream_t s);
 // mrts_engine.hip again (mrts_engine_bot_lds_bytes: mrts_bots.hip)
 hipError_t mrts_engine_masks_packed(const EngineParams *p, hipStream_t s, int32_t *packed);
 hipError_t mrts_engine_render(const EngineParams *p, hipStream_t s, int game, int map, int size, uint8_t *rgb);

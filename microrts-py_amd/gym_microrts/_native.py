@@ -115,6 +115,9 @@ SIGNATURES = {
     "mrts_unpack_masks": (ctypes.c_int, [P, P, ctypes.c_int32, ctypes.c_int32, P, P]),
     "mrts_unpack_obs": (ctypes.c_int, [P, P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, P]),
     "mrts_pack_obs": (ctypes.c_int, [P, P, ctypes.c_int64, ctypes.c_int32, ctypes.c_int32, P]),
+    "mrts_obs_conv_workspace_bytes": (ctypes.c_int64, [ctypes.c_int32] * 5),
+    "mrts_obs_conv_forward": (ctypes.c_int, [P, P] + [ctypes.c_int32] * 4 + [P, P, ctypes.c_int32, P]),
+    "mrts_obs_conv_backward": (ctypes.c_int, [P, P] + [ctypes.c_int32] * 4 + [P, P, ctypes.c_int32, P, P, ctypes.c_int64, P, P]),
     "mrts_policy_sample_packed": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
                                                  ctypes.c_uint32, P, P, P]),
     "mrts_policy_evaluate_packed": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P]),
