@@ -146,6 +146,28 @@ int mrts_set_bot_fusion(mrts_vec *h, int32_t on);
  * row. */
 int mrts_set_mask_delta(mrts_vec *h, int32_t on);
 
+/* Delta observations (default on; dense obs, int32 or float32).  A cell's obs row --
+ * its P planes -- is a function of the cell's unit, its action and the terrain,
+ * and all but about 2 % of the rows stay the same from tick to tick.  With delta observations, a step
+ * whose `obs` is the buffer that the last launch which wrote every obs row wrote to
+ * (mrts_reset, mrts_load_state, a step) stores only the rows whose content differs
+ * from the one of the state it loads.  mrts_reset_games and mrts_park_games into
+ * that buffer keep it current (they write their games' rows in full); given another
+ * buffer they end it.  A step given any other pointer writes every row, and that
+ * pointer is the current buffer from then on.  The bytes in the buffer are the same
+ * either way, PROVIDED nobody else writes it: the engine owns the obs buffer between
+ * steps (callers read or copy it, as the reference's rollout loop does).  A caller
+ * that wrote into it calls mrts_invalidate_obs -- the next step then writes every
+ * row -- or turns delta observations off.  on = 0: every step writes every row.
+ * Packed obs (MRTS_OBS_PACKED) are always written in full, and so are the obs of
+ * engines with partial observability (their rows also depend on the sight disks;
+ * measured slower) and of maps of more than four cells per lane of the step
+ * workgroup (more than 1024 cells). */
+int mrts_set_obs_delta(mrts_vec *h, int32_t on);
+/* The caller wrote into an obs buffer it gave to the engine: the next step writes
+ * every row of its `obs`, whichever buffer that is. */
+int mrts_invalidate_obs(mrts_vec *h);
+
 /* step_async + JNIGridnetVecClient.gameStep (vec_env.py:968-984, 1002):
  * actions [N][H*W][7] int64 (device), source [N][H*W] int32 = the source
  * channel of the last mrts_get_masks (selects the rows, vec_env.py:974).

@@ -207,6 +207,27 @@ struct mrts_vec {
     // and any of the launches above that fails while masks are bound clears it.
     int mask_delta = 1;          // requested
     bool masks_synced = false;
+    // delta obs (mrts_set_obs_delta; dense obs kinds): k_step stores only the obs rows whose one-hot
+    // word differs from the loaded state's, which needs every row of the step's obs buffer to be the
+    // one-hot of the stored state (parked games: zeros).  The obs pointer arrives per call, so the engine
+    // remembers obs_synced_ptr: the buffer it knows to be that, or null.  Every entry point that changes
+    // the game state or writes obs, and its effect:
+    //   mrts_bind_workspace      cleared (new state memory)
+    //   mrts_reset               set to its obs (k_reset writes every game's rows)
+    //   mrts_step / _weighted / mrts_step_group
+    //                            all through step_engines: a step into obs_synced_ptr runs delta and leaves
+    //                            it; a step into any other pointer, or with delta off, runs dense and sets
+    //                            it to that pointer; a failed bot or step launch: cleared
+    //   mrts_load_state          cleared once the state copy is queued, set to its obs by its outputs launch
+    //   mrts_reset_games / mrts_park_games
+    //                            left alone when given obs_synced_ptr: k_reset writes the listed games' rows
+    //                            in full (zeros for parked ones), the others are untouched, and a parked
+    //                            game's k_step returns before any write; cleared when given another pointer
+    //                            (those games' rows in the remembered buffer are stale) or when they fail
+    //   mrts_invalidate_obs      cleared: the way a caller who wrote into the buffer hands it back
+    //   everything else          no effect (neither the state nor an obs buffer changes)
+    int obs_delta = 1;           // requested
+    const void *obs_synced_ptr = nullptr;
 };
 
 // the launches that write the bound mask buffers report here: `dense` = every game's rows
@@ -219,6 +240,21 @@ static void masks_written(mrts_vec *h, hipError_t e, bool dense) {
 // most 16 cells per lane of the narrowest step workgroup (every map mrts_create accepts)
 static bool delta_ok(const mrts_vec *h) {
     return h->mask_delta && h->masks_synced && h->next_mask && h->HW <= 16 * mrts_engine_step_layout(h->HW, h->W, 0, 0, 0).NT;
+}
+
+// the launches that write obs report here: `dense` = every game's rows, into `obs`
+static void obs_written(mrts_vec *h, hipError_t e, const void *obs, bool dense) {
+    if (e) h->obs_synced_ptr = nullptr;
+    else if (dense) h->obs_synced_ptr = obs;
+}
+// delta obs needs the old one-hot words of a lane's cells in its registers: at most MRTS_OBS_DELTA_CELLS
+// cells per lane of the map's own (narrowest) step workgroup, so k_step never sees a size it cannot
+// serve; larger maps step dense.  Packed obs are 4 bytes per cell as it is: always in full.  Fog engines
+// step dense too: their rows depend on the sight disks, and building the loaded state's disks cost more
+// than the stores saved (partial_obs workload 78.5 -> 76.7 M env-steps/s, profiles/obs_delta/README.md).
+static bool obs_delta_ok(const mrts_vec *h, const void *obs) {
+    return h->obs_delta && h->obs_kind != MRTS_OBS_PACKED && !h->partial_obs && obs && h->obs_synced_ptr == obs &&
+           h->HW <= MRTS_OBS_DELTA_CELLS * mrts_engine_step_layout(h->HW, h->W, 0, 0, 0).NT;
 }
 
 static int fail(mrts_vec *h, int code, const std::string &msg) {
@@ -359,6 +395,7 @@ int mrts_bind_workspace(mrts_vec *h, void *dev, void *stream) {
     hipStream_t s = (hipStream_t)stream;
     h->bots_ready = false;
     h->masks_synced = false;
+    h->obs_synced_ptr = nullptr;
     h->ws = (unsigned char *)dev;
     std::vector<int32_t> genv((size_t)h->ngames * MRTS_GENV_WORDS, 0);
     for (int g = 0; g < h->ngames; g++) genv[(size_t)g * MRTS_GENV_WORDS + MRTS_G_MAP] = h->game_map[g];
@@ -446,6 +483,18 @@ int mrts_set_mask_delta(mrts_vec *h, int32_t on) {
     return MRTS_OK;
 }
 
+int mrts_set_obs_delta(mrts_vec *h, int32_t on) {
+    if (!h) return fail(h, MRTS_EINVAL, "set_obs_delta: null handle");
+    h->obs_delta = on ? 1 : 0;   // obs_synced_ptr stays: a dense step keeps the buffer in sync too
+    return MRTS_OK;
+}
+
+int mrts_invalidate_obs(mrts_vec *h) {
+    if (!h) return fail(h, MRTS_EINVAL, "invalidate_obs: null handle");
+    h->obs_synced_ptr = nullptr;
+    return MRTS_OK;
+}
+
 // the parameters of a launch that writes obs and, when bound, the next tick's masks and sources
 static EngineParams out_params(const mrts_vec *h, void *obs) {
     EngineParams p = h->base;
@@ -461,6 +510,7 @@ int mrts_reset(mrts_vec *h, void *stream, void *obs) {
     hipStream_t s = (hipStream_t)stream;
     hipError_t e = mrts_engine_reset(&p, s, nullptr, nullptr, 0);
     masks_written(h, e, true);
+    obs_written(h, e, obs, true);
     if (!e) e = bots_after_reset(h, s, nullptr, 0);
     return e ? hip_fail(h, e, "reset launch") : MRTS_OK;
 }
@@ -499,6 +549,7 @@ static EngineParams step_params(const mrts_vec *h, const mrts_step_io &io) {
         p.shaping = h->shaping;
     }
     p.mask_delta = delta_ok(h) ? 1 : 0;
+    p.obs_delta = obs_delta_ok(h, io.obs) ? 1 : 0;
     return p;
 }
 
@@ -612,8 +663,8 @@ int mrts_step_group_plan(mrts_vec *const *hs, int32_t n, int32_t policy, int32_t
 
 // The one step path: n engines under a group policy.  Per member: its parameters, k_bot when
 // the tick's bot decisions are not there yet, bot fusion; then the plan and, per launch, k_step
-// and what it means for the members' masks_synced and bots_ready.  A failed bot or step launch
-// while masks are bound clears that member's masks_synced.  `what` opens the error text.
+// and what it means for the members' masks_synced, obs_synced_ptr and bots_ready.  A failed bot or step
+// launch clears that member's obs_synced_ptr and, while masks are bound, its masks_synced.  `what` opens the error text.
 static int step_engines(mrts_vec *const *hs, int n, hipStream_t s, const mrts_step_io *io, int policy, const char *what) {
     EngineParams ps[MRTS_STEP_GROUP_MAX];
     for (int i = 0; i < n; i++) {
@@ -622,6 +673,7 @@ static int step_engines(mrts_vec *const *hs, int n, hipStream_t s, const mrts_st
         hipError_t e = h->bots_ready ? hipSuccess : mrts_engine_bots(&ps[i], s);
         if (e) {
             masks_written(h, e, false);
+            obs_written(h, e, io[i].obs, false);
             return group_fail(hs, i, MRTS_EHIP, std::string(what) + " bot launch: " + hipGetErrorString(e));
         }
         h->bots_ready = true;   // this tick's decisions are in botpa now, whatever happens below
@@ -643,6 +695,7 @@ static int step_engines(mrts_vec *const *hs, int n, hipStream_t s, const mrts_st
         for (int i = 0; i < n; i++)
             if (launch_of[i] == l) {
                 masks_written(hs[i], e, !ps[i].mask_delta);
+                obs_written(hs[i], e, io[i].obs, !ps[i].obs_delta);
                 hs[i]->bots_ready = ps[i].fuse_bots != 0;   // a fused step decided the next tick's
             }
         if (e) return group_fail(hs, first, MRTS_EHIP, std::string(what) + " launch: " + hipGetErrorString(e));
@@ -689,7 +742,10 @@ static int reset_listed(mrts_vec *h, hipStream_t s, const int32_t *games, const 
         h->parked[games[i]] = park;
     }
     hipError_t e = flags_changed ? upload_parked(h, s) : hipSuccess;
-    if (e) return hip_fail(h, e, (what + " parked flags upload").c_str());
+    if (e) {
+        h->obs_synced_ptr = nullptr;
+        return hip_fail(h, e, (what + " parked flags upload").c_str());
+    }
     h->scratch_host.assign(games, games + count);
     if (!maps) maps = games;   // (map list unused for parked games)
     h->scratch_host.insert(h->scratch_host.end(), maps, maps + count);
@@ -703,6 +759,8 @@ static int reset_listed(mrts_vec *h, hipStream_t s, const int32_t *games, const 
     const hipError_t es = hipStreamSynchronize(s);
     if (!e) e = es;
     masks_written(h, e, false);   // the listed games' rows only
+    if (obs != h->obs_synced_ptr) h->obs_synced_ptr = nullptr;   // the games' rows in the remembered buffer are stale
+    obs_written(h, e, obs, false);
     return e ? hip_fail(h, e, (what + " launch").c_str()) : MRTS_OK;
 }
 
@@ -1010,6 +1068,7 @@ int mrts_load_state(mrts_vec *h, void *stream, const void *src, void *obs) {
     if (e) return hip_fail(h, e, "load_state header");
     e = hipMemcpyAsync(h->ws, (const unsigned char *)src + hdr.size(), h->total, hipMemcpyDeviceToDevice, s);
     h->masks_synced = false;   // the state is another one from here on, even if the copy failed
+    h->obs_synced_ptr = nullptr;
     if (e) return hip_fail(h, e, "load_state copy");
     // the host mirrors only once the workspace copy is queued: a failed copy leaves them as they were
     std::memcpy(h->game_map.data(), hdr.data() + sizeof sh, (size_t)h->ngames * sizeof(int32_t));
@@ -1019,6 +1078,7 @@ int mrts_load_state(mrts_vec *h, void *stream, const void *src, void *obs) {
     EngineParams p = out_params(h, obs);
     e = mrts_engine_outputs(&p, s);
     masks_written(h, e, true);
+    obs_written(h, e, obs, true);
     return e ? hip_fail(h, e, "load_state outputs launch") : MRTS_OK;
 }
 

@@ -95,6 +95,10 @@ __host__ __device__ inline int posbits_words(int HW, int W) { return pos_words_l
 __host__ __device__ inline int vis_words(int HW) { return HW / 32 + 1; }   // one player's visibility bits
 }  // namespace mrts
 
+// delta obs (EngineParams::obs_delta): a lane keeps a key of each of its cells in the loaded state in
+// registers through the tick (mrts_engine.hip obs_key), for at most this many cells per lane: every
+// prefetched size
+#define MRTS_OBS_DELTA_CELLS 4
 struct EngineParams {
     int4 *cells;            // [G][cstride] (the first HW records of each game's row)
     int cstride;            // int4 records between consecutive games' cells (>= HW)
@@ -117,6 +121,9 @@ struct EngineParams {
     int mask_delta;         // k_step: `mask` holds getMasks(0) of the state the step loads (mrts_capi.cpp keeps
                             // track), so only the rows that can differ are stored: the source rows of the loaded
                             // and of the final state (mrts_set_mask_delta); src_out is written in full either way
+    int obs_delta;          // k_step, dense obs: `obs` holds the one-hot rows of the state the step loads (mrts_capi.cpp
+                            // keeps track: obs_synced_ptr), so only the rows of cells whose content changed are stored
+                            // (mrts_set_obs_delta); at most MRTS_OBS_DELTA_CELLS cells per lane
     // optional fused step_wait outputs (vec_env.py:1057): reward = raw @ rw
     // (float64, k = 0..5 in order; channels 1..5 zeroed when !shaping) and done[:,0]
     double *reward;         // [N] or null

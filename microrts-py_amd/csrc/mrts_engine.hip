@@ -379,21 +379,51 @@ __device__ __forceinline__ void compute_vis(const EngineParams& p, const Lds& L)
     __syncthreads();
 }
 
-// phase A's one-hot word of cell c for every view of the game (into L.outw)
+// view v's one-hot word of cell c (unit u, action a, terrain wl; with fog, the sight disks in L.vis)
 template <int P>
-__device__ __forceinline__ void onehot_words(const EngineParams& p, const Lds& L, const Game& G, int c) {
-    const int HW = p.HW, nw = vis_words(HW);
+__device__ __forceinline__ uint32_t onehot_word(const EngineParams& p, const Lds& L, int c, int v, uint32_t u, uint32_t a, uint8_t wl) {
+    if (P == 31) {
+        const int nw = vis_words(p.HW);
+        const bool shown = u == 0 || u_owner(u) == v || ((L.vis[v * nw + (c >> 5)] >> (c & 31)) & 1u);
+        const bool opp = (L.vis[(1 - v) * nw + (c >> 5)] >> (c & 31)) & 1u;
+        return cell_onehot(u, a, wl, v, P, shown, opp);
+    }
+    return cell_onehot(u, a, wl, v);
+}
+// Delta obs (EngineParams::obs_delta): a one-hot word uses bits 0 .. P-1 (P <= 31); bit 31 carries
+// whether the cell's row is stored at all.  step_game keeps a key of every cell of the loaded state
+// and leaves it in L.outw, onehot_words marks the words of the cells whose key differs by now,
+// stream_obs_delta stores the marked rows.  The dense streams mask the bit off.
+constexpr uint32_t OBS_ROW_STORE = 1u << 31;
+// The key: everything cell_onehot reads of the cell, for every view at once, in 16 bits, so that a lane
+// holds two cells' keys per register (the views' full words would take four): the terrain bit, and for
+// a unit a mixed-radix number of its clamped hit points (5) and resources (5), owner (3), action type (6)
+// and type (7), 3150 values.  0 / 1: an empty cell.  Every view's word is a function of the key (the
+// views differ in how they read the owner), so an equal key means equal rows, and a changed key a
+// changed row in every view.  Full observability only: with fog the words also depend on the sight
+// disks, and the pass that builds the loaded state's disks cost more than the stores it saved
+// (profiles/obs_delta/README.md), so a fog engine steps dense (mrts_capi.cpp obs_delta_ok).
+constexpr int OBS_KEY_BITS = 16;
+template <int P>
+constexpr bool obs_delta_built = P == 29;
+__device__ __forceinline__ uint32_t obs_key(uint32_t u, uint32_t a, uint8_t wl) {
+    const uint32_t empty = wl ? 1u : 0u;
+    if (u == 0) return empty;
+    const int hp = min(max(u_hp(u), 0), 4), res = min(u_res(u), 4), ow = u_owner(u);
+    const int at = a ? min(code_type(act_code(a)), 5) : 0;
+    const uint32_t idx = ((((uint32_t)hp * 5u + (uint32_t)res) * 3u + (uint32_t)(ow < 0 ? 0 : min(ow, 1) + 1)) * 6u + (uint32_t)at) * 7u +
+                         (uint32_t)min(u_type(u), 6);   // < 3150
+    return ((idx + 1u) << 1) | empty;   // 2 .. 6301
+}
+// phase A's one-hot word of cell c for every view of the game (into L.outw); `delta`: L.outw[c] holds
+// the cell's key in the loaded state, and the words of a cell whose key differs are marked OBS_ROW_STORE
+template <int P>
+__device__ __forceinline__ void onehot_words(const EngineParams& p, const Lds& L, const Game& G, int c, bool delta = false) {
+    const int HW = p.HW;
     const uint32_t u = L.unit[c], a = L.act[c];
     const uint8_t wl = L.wall[c];
-    for (int v = 0; v < G.nviews; v++) {
-        if (P == 31) {
-            const bool shown = u == 0 || u_owner(u) == v || ((L.vis[v * nw + (c >> 5)] >> (c & 31)) & 1u);
-            const bool opp = (L.vis[(1 - v) * nw + (c >> 5)] >> (c & 31)) & 1u;
-            L.outw[v * HW + c] = cell_onehot(u, a, wl, v, P, shown, opp);
-        } else {
-            L.outw[v * HW + c] = cell_onehot(u, a, wl, v);
-        }
-    }
+    const uint32_t mark = obs_delta_built<P> && delta && obs_key(u, a, wl) != L.outw[c] ? OBS_ROW_STORE : 0u;
+    for (int v = 0; v < G.nviews; v++) L.outw[v * HW + c] = onehot_word<P>(p, L, c, v, u, a, wl) | mark;
 }
 // Delta masks (EngineParams::mask_delta): a row's third word carries, above its 15
 // mask bits (a row is 79 of the words' 96 bits), whether the row is stored at all.
@@ -420,6 +450,7 @@ template <int P, typename OT>
 __device__ __forceinline__ void stream_obs(const EngineParams& p, const Lds& L, const Game& G, int t0, int nt) {
     const int HW = p.HW, NV = G.nviews;
     const uint32_t* ow = L.outw;
+    auto word = [&](int i) { return ow[i] & ~OBS_ROW_STORE; };   // (a word's store mark is the delta stream's)
     OT* out = reinterpret_cast<OT*>(p.obs) + (size_t)G.env0 * HW * P;
     const int total = NV * HW * P;
     if (((HW * P) & 3) == 0) {   // every env's rows start 16-B aligned
@@ -437,12 +468,12 @@ __device__ __forceinline__ void stream_obs(const EngineParams& p, const Lds& L, 
         // clamped into the word region (its last trip's values are never used).
         const int dq = 4 * nt / P, dr = 4 * nt - dq * P, cmax = NV * HW - 1;
         int c = 4 * t0 / P, pl = 4 * t0 - c * P;
-        uint32_t w0 = ow[min(c, cmax)], w1 = ow[min(c, cmax) + 1];
+        uint32_t w0 = word(min(c, cmax)), w1 = word(min(c, cmax) + 1);
         for (int k = t0; k < total / 4; k += nt) {
             int cn = c + dq, pn = pl + dr;
             if (pn >= P) { pn -= P; cn++; }
             const int cr = min(cn, cmax);
-            const uint32_t n0 = ow[cr], n1 = ow[cr + 1];
+            const uint32_t n0 = word(cr), n1 = word(cr + 1);
             const uint32_t bits = (w0 >> pl) | (w1 << (P - pl));
             st16(out + 4 * k, (bits & 1u) ? ONE : 0, (bits & 2u) ? ONE : 0, (bits & 4u) ? ONE : 0, (bits & 8u) ? ONE : 0);
             w0 = n0;
@@ -473,11 +504,39 @@ __device__ __forceinline__ void stream_obs_words(const EngineParams& p, const Ld
         for (int i = t0; i < n; i += nt) out[i] = (int32_t)ow[i];
     }
 }
-// phase B's obs of every view in the engine's obs kind
+// phase B's obs rows with delta obs: only the rows whose word is marked OBS_ROW_STORE (a few of a
+// game's NV HW; the others hold these bytes already).  Each wave scans 64 words per trip, one per lane,
+// and stores the marked rows two per instruction: lanes 0..P-1 one row, lanes 32..32+P-1 the next, a
+// plane (4 bytes: a row is only 4-byte aligned) per lane.  Reads nothing but the words and kernel
+// parameters, as phase B must.  Lanes t0 .. t0 + nt as the other streams; nt is a multiple of 64.
 template <int P, typename OT>
-__device__ __forceinline__ void stream_obs_kind(const EngineParams& p, const Lds& L, const Game& G, int t0, int nt) {
-    if constexpr (obs_packed<OT>) stream_obs_words(p, L, G, t0, nt);
-    else stream_obs<P, OT>(p, L, G, t0, nt);
+__device__ __forceinline__ void stream_obs_delta(const EngineParams& p, const Lds& L, const Game& G, int t0, int nt) {
+    static_assert(sizeof(OT) == 4 && P <= 31, "a plane per lane, half a wave per row; bit 31 is the mark");
+    constexpr uint32_t ONE = std::is_same<OT, float>::value ? 0x3f800000u : 1u;   // 1.0f or 1 as stored bits
+    const int rows = G.nviews * p.HW, lane = t0 & 63, pl = lane & 31;
+    const uint32_t* ow = L.outw;
+    uint32_t* out = reinterpret_cast<uint32_t*>(p.obs) + (size_t)G.env0 * p.HW * P;
+    for (int base = t0 - lane; base < rows; base += nt) {   // wave-uniform
+        const int r = base + lane;
+        unsigned long long m = __ballot(r < rows && (ow[r] & OBS_ROW_STORE) != 0);
+        while (m) {
+            int b = __builtin_ctzll(m);   // the low half's row
+            m &= m - 1;
+            if (lane >= 32) b = m ? __builtin_ctzll(m) : -1;   // the high half's: the next marked one, if any
+            m &= m - 1;   // (0 stays 0)
+            if (b >= 0 && pl < P) out[(size_t)(base + b) * P + pl] = ((ow[base + b] >> pl) & 1u) ? ONE : 0u;
+        }
+    }
+}
+// phase B's obs of every view in the engine's obs kind; `delta`: only the marked rows (dense kinds)
+template <int P, typename OT>
+__device__ __forceinline__ void stream_obs_kind(const EngineParams& p, const Lds& L, const Game& G, int t0, int nt, bool delta = false) {
+    if constexpr (obs_packed<OT>) {
+        stream_obs_words(p, L, G, t0, nt);
+    } else {
+        if (delta) stream_obs_delta<P, OT>(p, L, G, t0, nt);
+        else stream_obs<P, OT>(p, L, G, t0, nt);
+    }
 }
 // phase B's mask rows of every view, lanes t0 .. t0 + nt
 __device__ __forceinline__ void stream_masks(const EngineParams& p, const Lds& L, const Game& G, int t0, int nt) {
@@ -573,9 +632,13 @@ __device__ __forceinline__ void stream_masks_delta(const EngineParams& p, const 
 // mask stores drain; one more barrier before the obs stream.
 // `delta` (k_step with EngineParams::mask_delta): the mask rows' third words arrive
 // preset with MASK_ROW_STORE and only the marked rows are stored (stream_masks_delta).
+// `odelta` (k_step with EngineParams::obs_delta): L.outw[0, HW) arrives holding the cells' keys
+// (obs_key) in the loaded state, written by the lanes that own the cells in phase A or, on the
+// early path, ahead of a barrier; only the rows of cells whose key changed are stored (stream_obs_delta).
 template <int NT, int P, typename OT>
 __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L, const Game& G, bool obs, bool masks, int res0,
-                                             int res1, int skip = 0, int* early_cnt = nullptr, bool delta = false) {
+                                             int res1, int skip = 0, int* early_cnt = nullptr, bool delta = false,
+                                             bool odelta = false) {
     const int HW = p.HW;
     if (skip == 0 && obs && masks) {
         const int nw = vis_words(HW);
@@ -595,16 +658,16 @@ __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L
             }
             __syncthreads();
         }
-        for (int c = threadIdx.x; c < HW; c += NT) onehot_words<P>(p, L, G, c);
+        for (int c = threadIdx.x; c < HW; c += NT) onehot_words<P>(p, L, G, c, odelta);
         __syncthreads();
-        stream_obs_kind<P, OT>(p, L, G, threadIdx.x, NT);
+        stream_obs_kind<P, OT>(p, L, G, threadIdx.x, NT, odelta);
         MRTS_STAMP_MAX(9, (threadIdx.x & 63) == 0);
         return;
     }
     if (obs && P == 31) compute_vis<NT>(p, L);
     const int a0 = early_cnt ? skip : 0;   // phase A's first lane
     for (int c = (int)threadIdx.x - a0; c < HW; c += NT - a0) {
-        if (obs) onehot_words<P>(p, L, G, c);
+        if (obs) onehot_words<P>(p, L, G, c, odelta);
         if (masks) mask_words(p, L, G, c, res0, res1, delta);
     }
     if (early_cnt) {   // the streaming waves' own meeting point (wave 0 never arrives)
@@ -626,7 +689,7 @@ __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L
     MRTS_STAMP(8, (int)threadIdx.x == skip);
     __builtin_amdgcn_s_setprio(0);
     const int t0 = (int)threadIdx.x - skip, nt = NT - skip;
-    if (obs) stream_obs_kind<P, OT>(p, L, G, t0, nt);
+    if (obs) stream_obs_kind<P, OT>(p, L, G, t0, nt, odelta);
     if (masks && delta) stream_masks_delta(p, L, G, t0, nt);
     else if (masks) stream_masks(p, L, G, t0, nt);
     MRTS_STAMP_MAX(9, (threadIdx.x & 63) == 0);
@@ -1219,6 +1282,26 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
         load_game<NT>(p, L, g);
     }
     MRTS_STAMP(3, threadIdx.x == 0);
+    // delta obs: the keys (obs_key) of this lane's cells in the state just loaded -- of what the obs buffer
+    // holds -- kept in registers until the tick is over (at most MRTS_OBS_DELTA_CELLS cells per lane:
+    // mrts_capi.cpp obs_delta_ok)
+    bool odelta = false;
+    constexpr int KB = OBS_KEY_BITS, KPR = 32 / KB;   // bits per key, keys per register
+    uint32_t okey[MRTS_OBS_DELTA_CELLS / KPR] = {};
+    if constexpr (!obs_packed<OT> && obs_delta_built<P>) {
+        odelta = p.obs_delta != 0;
+        if (odelta) {
+#pragma unroll
+            for (int k = 0; k < MRTS_OBS_DELTA_CELLS; k++) {
+                const int c = (int)threadIdx.x + k * NT;
+                if (c < HW) {
+                    const uint32_t u = L.unit[c], a = L.act[c];
+                    const uint8_t wl = L.wall[c];
+                    okey[k / KPR] |= obs_key(u, a, wl) << (k % KPR * KB);
+                }
+            }
+        }
+    }
     const int time = L.sc[SC_TIME];
     const int steps0 = L.sc[SC_STEPS], map_now = L.sc[SC_MAP];   // read before any lane can rewrite them (auto-reset)
     // bot-vs-bot game (MicroRTSBotVecEnv): player 0's PlayerAction comes from k_bot too
@@ -1570,14 +1653,30 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     if (delta)
         for (int c = threadIdx.x, k = 0; c < HW; c += NT, k++)
             for (int v = 0; v < G.nviews; v++) L.outm[3 * (v * HW + c) + 2] = ((was_src >> (2 * k + v)) & 1u) ? MASK_ROW_STORE : 0u;
+    // Delta obs: each lane leaves its cells' old keys where phase A writes the new one-hot words (L.outw:
+    // dead scratch lists, or a bot game's own region) and reads them back on the same lane.  On the early
+    // path L.outw is the uid array, which the bot's setup reads up to its inner barrier, and phase A runs
+    // on other lanes: the keys go in behind the setup (whose last loop does not touch the uid array) and
+    // ahead of the barrier that follows it.
+    auto old_keys = [&]() {
+#pragma unroll
+        for (int k = 0; k < MRTS_OBS_DELTA_CELLS; k++) {
+            const int c = (int)threadIdx.x + k * NT;
+            if (c < HW)
+                L.outw[c] = (okey[k / KPR] >> (k % KPR * KB)) & ((1u << KB) - 1u);
+        }
+    };
+    if (odelta && !early) old_keys();
     if (early) {
         __syncthreads();
         bot_setup_workgroup<NT>(p, F.B);
+        if (odelta) old_keys();
         __syncthreads();
         MRTS_STAMP(14, threadIdx.x == 0);
     }
     if (!early || threadIdx.x >= 64)
-        emit_outputs<NT, P, OT>(p, L, G, true, p.mask != nullptr, res0, res1, botg ? 64 : 0, early ? F.early_cnt : nullptr, delta);
+        emit_outputs<NT, P, OT>(p, L, G, true, p.mask != nullptr, res0, res1, botg ? 64 : 0, early ? F.early_cnt : nullptr, delta,
+                                odelta);
     if (FB && botg && threadIdx.x < 64) {
         if (early) __builtin_amdgcn_s_setprio(3);   // the latency-bound bot wave first; the streaming waves are memory-bound
         bots::bot_game<true>(p, g - p.nsp_games, 1, F.B, L.sc, pf_ok, pf.aa, pf.aa2, early);

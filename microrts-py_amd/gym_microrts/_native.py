@@ -126,6 +126,8 @@ SIGNATURES = {
     "mrts_bind_mask_outputs": (ctypes.c_int, [P, P, P]),
     "mrts_set_bot_fusion": (ctypes.c_int, [P, ctypes.c_int32]),
     "mrts_set_mask_delta": (ctypes.c_int, [P, ctypes.c_int32]),
+    "mrts_set_obs_delta": (ctypes.c_int, [P, ctypes.c_int32]),
+    "mrts_invalidate_obs": (ctypes.c_int, [P]),
     "mrts_render": (ctypes.c_int, [P, P, ctypes.c_int32, P, ctypes.c_int32]),
     "mrts_error_flags": (ctypes.c_int, [P, P, P]),
     "mrts_state_bytes": (ctypes.c_size_t, [P]),

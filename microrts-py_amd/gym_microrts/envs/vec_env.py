@@ -202,6 +202,7 @@ class MicroRTSGridModeVecEnv:
         eager_masks=True,
         bot_fusion=True,
         mask_delta=None,
+        obs_delta=None,
         game_offset=0,
         obs_format="dense",
         _ai1s=None,
@@ -222,7 +223,16 @@ class MicroRTSGridModeVecEnv:
         holds the same bytes either way, but while masks are eager it belongs to the
         engine between steps: read or copy it, do not write into it.  A caller that did
         write into it calls mrts_bind_mask_outputs again (the next step then rewrites
-        every row) or passes mask_delta=False."""
+        every row) or passes mask_delta=False.
+
+        obs_delta (dense obs under full observability only; None = on, unless the environment variable
+        MICRORTS_AMD_OBS_DELTA=0): step() stores only the obs rows -- a cell's P planes --
+        whose one-hot word differs from the one of the state the step loaded, instead of
+        all N * H*W of them (mrts_set_obs_delta).  The obs hold the same bytes either way,
+        but on the tensor and hybrid contracts the returned obs tensor is the engine's
+        between steps: read or copy it (as the reference's rollout loop does), do not
+        write into it.  A caller that did write into it calls invalidate_obs() (the next
+        step then rewrites every row) or passes obs_delta=False."""
         # vec_env.py:110-127
         self.num_selfplay_envs = num_selfplay_envs
         self.num_bot_envs = num_bot_envs
@@ -350,6 +360,11 @@ class MicroRTSGridModeVecEnv:
             mask_delta = os.environ.get("MICRORTS_AMD_MASK_DELTA", "1").strip() != "0"
         self.mask_delta = bool(mask_delta)
         _native.check(_native.lib().mrts_set_mask_delta(self._h, int(self.mask_delta)), self._h, "set_mask_delta")
+        # delta obs: a step stores only the obs rows that changed (mrts_set_obs_delta)
+        if obs_delta is None:
+            obs_delta = os.environ.get("MICRORTS_AMD_OBS_DELTA", "1").strip() != "0"
+        self.obs_delta = bool(obs_delta)
+        _native.check(_native.lib().mrts_set_obs_delta(self._h, int(self.obs_delta)), self._h, "set_obs_delta")
 
         # computed properties (vec_env.py:230-254)
         self.action_space_dims = [6, 4, 4, 4, 4, len(self.utt["unitTypes"]), 7 * 7]
@@ -432,6 +447,11 @@ class MicroRTSGridModeVecEnv:
         _native.check(_native.lib().mrts_reset(self._h, self._stream(), self._obs.data_ptr()), self._h, "reset")
         self._mask_fresh = self.eager_masks
         return self._obs_out()
+
+    def invalidate_obs(self):
+        """Hand the obs tensor back after writing into it (mrts_invalidate_obs): the next
+        step writes every obs row again, whatever obs_delta says."""
+        _native.check(_native.lib().mrts_invalidate_obs(self._h), self._h, "invalidate_obs")
 
     def get_action_mask(self):
         """vec_env.py:1091-1101: (N, H*W, 78); channel 0 kept as source_unit_mask.
@@ -915,7 +935,7 @@ class MicroRTSMixedMapVecEnv:
       mask = env.get_action_mask()             # list over buckets
       obs, rew, done, infos = env.step(actions)  # actions: list over buckets
 
-    Keyword arguments (mask_delta and obs_format among them) go to every bucket's engine.
+    Keyword arguments (mask_delta, obs_delta and obs_format among them) go to every bucket's engine.
     """
 
     def __init__(self, buckets, concurrent=False, group_policy="default", **common):
@@ -1060,7 +1080,7 @@ class MicroRTSSizeCyclingVecEnv:
 
     def __init__(self, num_selfplay_envs, num_bot_envs, ai2s=[], map_paths=["maps/16x16/basesWorkers16x16.xml"], cycle_maps=[],
                  max_steps=2000, partial_obs=False, reward_weight=np.array([0.0, 1.0, 0.0, 0.0, 0.0, 5.0]), device=None,
-                 obs_dtype=None, mask_delta=None, obs_format="dense"):
+                 obs_dtype=None, mask_delta=None, obs_format="dense", obs_delta=None):
         self.num_selfplay_envs, self.num_bot_envs = num_selfplay_envs, num_bot_envs
         self.obs_format = obs_format   # every size engine's (MicroRTSGridModeVecEnv: obs entries [N, H_i, W_i] int32 when "packed")
         self.num_envs = num_selfplay_envs + num_bot_envs
@@ -1083,7 +1103,7 @@ class MicroRTSSizeCyclingVecEnv:
             maps_i = [m if self._size_of[m] == sz else own[0] for m in per_env]   # placeholders are parked at reset
             self.envs.append(MicroRTSGridModeVecEnv(num_selfplay_envs, num_bot_envs, partial_obs=partial_obs, max_steps=max_steps,
                                                     ai2s=ai2s, map_paths=maps_i, reward_weight=reward_weight, device=device,
-                                                    return_tensors=True, obs_dtype=obs_dtype, mask_delta=mask_delta,
+                                                    return_tensors=True, obs_dtype=obs_dtype, mask_delta=mask_delta, obs_delta=obs_delta,
                                                     obs_format=obs_format, _extra_maps=own))
         self.device = self.envs[0].device
         self.reward_weight = reward_weight
