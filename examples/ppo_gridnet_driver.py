@@ -28,6 +28,9 @@ envs) runs end to end on the GPU.
   --head fused : gym_microrts.policy_head -- the head as HIP kernels that read only the
                  rows of cells holding a unit that can act (sample in the rollout,
                  evaluate + its backward in the update); --api tensor only
+  --actions packed : with --head fused, one 32-bit word per cell from the head to the step
+                 (action_format="packed", gym_microrts.packed_actions): the rollout buffer keeps
+                 the words -- 4 bytes a cell against 56 -- and the update evaluates from them
 
 With --api numpy / hybrid the rollout makes ppo_gridnet.py's own calls in its own
 forms (`torch.Tensor(envs.reset()).to(device)`, `torch.tensor(envs.get_action_mask())
@@ -207,15 +210,16 @@ def policy(net, obs, mask, hw, action=None):
     return a.reshape(-1, hw, len(NVEC)), logp.reshape(-1, hw).sum(1), ent.reshape(-1, hw).sum(1), value
 
 
-def policy_fused(net, obs, mask, source, action=None, seed=0, step=0):
+def policy_fused(net, obs, mask, source, action=None, seed=0, step=0, action_format="dense"):
     """policy() over gym_microrts.policy_head: mask / source are the engine's int32
     tensors (or the rollout buffer's copies of them), or mask is the packed form
     ([N, HW, 3] int32, get_action_mask_packed()) and source is None.  A component without a valid
     entry contributes 0 to the log-prob and the entropy (the reference's float32
-    result), where policy()'s log_softmax gives -log(len) and log(len)."""
+    result), where policy()'s log_softmax gives -log(len) and log(len).  action_format="packed": the
+    sampled actions are packed words [N, HW] int32; a given `action` of that form is recognised as it is."""
     logits, value = net(obs)
     if action is None:
-        action, logp, ent = policy_head.sample(logits, mask, source, seed=seed, step=step)
+        action, logp, ent = policy_head.sample(logits, mask, source, seed=seed, step=step, action_format=action_format)
     else:
         logp, ent = policy_head.evaluate(logits, mask, source, actions=action)
     return action, logp, ent, value
@@ -229,7 +233,7 @@ def bot_list(n):
 
 def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, updates=2, api="numpy", minibatches=4,
         epochs=2, seed=1, device="cuda", log=print, max_steps=2000, head="torch", keep_first_rollout=False, masks="dense",
-        obs="dense", encoder="torch"):
+        obs="dense", encoder="torch", actions="dense"):
     """head: "torch" or "fused" (policy_fused; --api tensor only).  keep_first_rollout: the
     returned stats carry "first_rollout" -- the first rollout's buffers and the weights
     that acted in it.  masks: "dense", or "packed" (--head fused only): the rollout buffer
@@ -238,7 +242,10 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
     (--api tensor only): the engine writes the packed obs words, the buffer holds them
     ([T, N, H, W] int32) and every forward reads packed_obs.unpack_obs of them -- the same
     float32 planes the dense run sees.  encoder: "torch", or "fused" (--obs packed only): the
-    network takes the words and its first stage is obs_conv.encode, so nothing is unpacked."""
+    network takes the words and its first stage is obs_conv.encode, so nothing is unpacked.
+    actions: "dense", or "packed" (--head fused only): the env takes one 32-bit word per cell, the head
+    writes the words, the buffer holds them ([T, N, HW] int32, 4 bytes a cell against 56) and the update
+    gathers and evaluates from them."""
     if head not in ("torch", "fused"):
         raise ValueError(f"head must be 'torch' or 'fused', not {head!r}")
     if head == "fused" and api != "tensor":
@@ -255,6 +262,11 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
         raise ValueError(f"encoder must be 'torch' or 'fused', not {encoder!r}")
     if encoder == "fused" and obs != "packed":
         raise ValueError("--encoder fused needs --obs packed: the fused first stage reads the packed words")
+    if actions not in ("dense", "packed"):
+        raise ValueError(f"actions must be 'dense' or 'packed', not {actions!r}")
+    if actions == "packed" and head != "fused":
+        raise ValueError("--actions packed needs --head fused: only the fused head writes and reads packed actions")
+    packed_a = actions == "packed"
     packed_o = obs == "packed"
     fused_enc = encoder == "fused"
     fused = head == "fused"
@@ -281,7 +293,7 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
                                              map_paths=["maps/16x16/basesWorkers16x16A.xml"],
                                              reward_weight=np.array([10.0, 1.0, 1.0, 0.2, 1.0, 4.0]),
                                              cycle_maps=["maps/16x16/basesWorkers16x16A.xml"], device=dev, return_tensors=True,
-                                             obs_format=obs)
+                                             obs_format=obs, action_format=actions)
     n, hw = envs.num_envs, envs.height * envs.width
     h, w, planes = envs.observation_space.shape
     net = GridNet(planes, h, w).to(dev)
@@ -302,7 +314,10 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
     else:
         buf_mask = torch.zeros((num_steps, n, hw, sum(NVEC)), device=dev, dtype=torch.int32 if fused else torch.float32)
     buf_src = torch.zeros((num_steps, n, hw), device=dev, dtype=torch.int32) if fused and not packed else None
-    buf_act = torch.zeros((num_steps, n, hw, len(NVEC)), dtype=torch.long, device=dev)
+    if packed_a:
+        buf_act = torch.zeros((num_steps, n, hw), dtype=torch.int32, device=dev)
+    else:
+        buf_act = torch.zeros((num_steps, n, hw, len(NVEC)), dtype=torch.long, device=dev)
     buf_logp, buf_rew, buf_done, buf_val = (torch.zeros((num_steps, n), device=dev) for _ in range(4))
 
     def as_dev(x):
@@ -335,7 +350,7 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
                 net_in = planes_of(next_obs, dense_obs)
                 if fused:
                     a, logp, _, v = policy_fused(net, net_in, buf_mask[t], None if packed else buf_src[t], seed=seed,
-                                                 step=update * num_steps + t)
+                                                 step=update * num_steps + t, action_format=actions)
                 else:
                     a, logp, _, v = policy(net, net_in, buf_mask[t], hw)
             buf_act[t], buf_logp[t], buf_val[t] = a, logp, v
@@ -510,8 +525,9 @@ if __name__ == "__main__":
     ap.add_argument("--masks", choices=["dense", "packed"], default="dense")
     ap.add_argument("--obs", choices=["dense", "packed"], default="dense")
     ap.add_argument("--encoder", choices=["torch", "fused"], default="torch")
+    ap.add_argument("--actions", choices=["dense", "packed"], default="dense")
     a = ap.parse_args()
     out = run(a.num_selfplay_envs, a.num_bot_envs, a.partial_obs, a.num_steps, a.updates, a.api, a.minibatches,
               log=lambda s: print(json.dumps(s), flush=True), max_steps=a.max_steps, head=a.head, masks=a.masks, obs=a.obs,
-              encoder=a.encoder)
+              encoder=a.encoder, actions=a.actions)
     print(json.dumps(out))

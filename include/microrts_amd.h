@@ -171,6 +171,9 @@ int mrts_invalidate_obs(mrts_vec *h);
 /* step_async + JNIGridnetVecClient.gameStep (vec_env.py:968-984, 1002):
  * actions [N][H*W][7] int64 (device), source [N][H*W] int32 = the source
  * channel of the last mrts_get_masks (selects the rows, vec_env.py:974).
+ * After mrts_set_action_format(h, MRTS_ACT_PACKED), `actions` is read as the packed
+ * words [N][H*W] int32 instead ("Packed actions" below), here and in
+ * mrts_step_weighted and mrts_step_group.
  * Outputs: obs, raw_reward [N][6] float64 (the six reward functions), done
  * [N][6] uint8.  Finished games auto-reset (terminal reward/done reported). */
 int mrts_step(mrts_vec *h, void *stream, const int64_t *actions, const int32_t *source,
@@ -356,6 +359,70 @@ int mrts_policy_evaluate_packed(void *stream, const float *logits, const int32_t
 int mrts_policy_evaluate_backward_packed(void *stream, const float *logits, const int32_t *packed, int32_t num_envs, int32_t hw,
                                          const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
                                          float *grad_logits);
+
+/* Packed actions: an action row's seven components in one 32-bit word per cell, the form a
+ * rollout buffer can afford to keep (4 bytes a cell against the int64 row's 56).
+ *   action_words [N][H*W] int32, holding uint32 bit patterns;
+ *   bits 0..2 action type, 3..4 move direction, 5..6 harvest direction, 7..8 return direction,
+ *   9..10 produce direction, 11..13 produce type, 14..19 attack cell: component k in the
+ *   fewest bits that hold its entries, laid end to end;
+ *   bit 20 + k, k = 0..6, is the INVALID flag of component k;
+ *   bits 27..31 are zero in everything this library writes, and every reader ignores them.
+ * Meaning: a word stands for the dense row whose component k is -1 when flag k is set and
+ * the field's value otherwise (so a type field of 6 or 7, a produce type of 7 and an attack
+ * cell of 49..63 are out of range exactly as the same int64 values are), and every reader
+ * -- the step's decode, the action head's evaluate -- treats a word exactly as the dense
+ * reader treats that row.  Packing an int64 row puts component k into its field when it lies
+ * in [0, 2^bits_k); otherwise the field is 0 and flag k is set.  Hence unpack(pack(a)) == a
+ * for every row whose components fit their fields (all that the samplers and the action
+ * head ever write), and step / evaluate of pack(a) equal those of a for ANY int64 row: a
+ * component that does not fit its field is out of range in the dense form as well.
+ *
+ * mrts_set_action_format: what the `actions` pointer of mrts_step, mrts_step_weighted and
+ * this engine's member of mrts_step_group holds from now on -- MRTS_ACT_DENSE (default):
+ * [N][H*W][7] int64; MRTS_ACT_PACKED: the words, [N][H*W] int32 behind the same pointer
+ * type, 4-byte aligned (MRTS_EINVAL otherwise).  A per-engine setting like
+ * mrts_set_mask_delta: one grouped launch may hold engines of either kind.  It changes no
+ * game state and is not part of a snapshot's fingerprint: a state saved by an engine of
+ * one format loads into an engine of the other.  MRTS_EINVAL for a null handle or any
+ * other format value. */
+#define MRTS_ACT_DENSE 0
+#define MRTS_ACT_PACKED 1
+int mrts_set_action_format(mrts_vec *h, int32_t format);
+
+/* mrts_sample_actions_src's stream and picks, stored as packed action words [num_envs][hw]
+ * int32: exactly pack of the rows mrts_sample_actions_src writes.  The same checks, `words`
+ * 4-byte aligned.  (The dense mrts_sample_actions and the grouped sampler have no packed twin.) */
+int mrts_sample_actions_src_packed(void *stream, const int32_t *mask, const int32_t *source, int32_t num_envs, int32_t hw,
+                                   int32_t env0, uint64_t seed, uint32_t step, int32_t *words);
+
+/* The converters between int64 rows [rows][7] and words [rows], by the rules above (unpack
+ * writes every element).  rows up to 2^31 - 257; MRTS_EINVAL before any launch for a null
+ * pointer, rows out of range, `actions` not 8-byte or `words` not 4-byte aligned; rows == 0
+ * is MRTS_OK and launches nothing.  16-byte accesses on the int64 side when it is 16-byte
+ * aligned.  They run on `stream`, allocate and synchronise nothing. */
+int mrts_pack_actions(void *stream, const int64_t *actions, int64_t rows, int32_t *words);
+int mrts_unpack_actions(void *stream, const int32_t *words, int64_t rows, int64_t *actions);
+
+/* The action head with both formats as arguments: mask_format MRTS_MASK_DENSE (`mask`
+ * [num_envs][hw][78] with `source`) or MRTS_MASK_PACKED (`mask` is the packed words
+ * [num_envs][hw][3], `source` is not read and may be NULL); action_format MRTS_ACT_DENSE
+ * (`actions` [num_envs][hw][7] int64, 8-byte aligned) or MRTS_ACT_PACKED (the words
+ * [num_envs][hw] int32, 4-byte aligned).  Everything else is mrts_policy_sample's,
+ * mrts_policy_evaluate's and mrts_policy_evaluate_backward's contract word for word, and the
+ * results are theirs bit for bit: sample's words are pack of the dense call's actions, and
+ * evaluate reads a word as the row it stands for (a flagged component is an action outside
+ * its range: exactly -1e8).  MRTS_EINVAL also for any other format value. */
+#define MRTS_MASK_DENSE 0
+#define MRTS_MASK_PACKED 1
+int mrts_policy_sample_fmt(void *stream, const float *logits, int32_t mask_format, const int32_t *mask, const int32_t *source,
+                           int32_t num_envs, int32_t hw, int32_t env0, uint64_t seed, uint32_t step, int32_t action_format,
+                           void *actions, float *logprob, float *entropy);
+int mrts_policy_evaluate_fmt(void *stream, const float *logits, int32_t mask_format, const int32_t *mask, const int32_t *source,
+                             int32_t num_envs, int32_t hw, int32_t action_format, const void *actions, float *logprob, float *entropy);
+int mrts_policy_evaluate_backward_fmt(void *stream, const float *logits, int32_t mask_format, const int32_t *mask, const int32_t *source,
+                                      int32_t num_envs, int32_t hw, int32_t action_format, const void *actions,
+                                      const float *grad_logprob, const float *grad_entropy, float *grad_logits);
 
 /* Packed observations: the one-hot obs as the 32-bit word per cell the engine builds
  * it from, the form a rollout buffer can afford to keep (4 bytes a cell against the

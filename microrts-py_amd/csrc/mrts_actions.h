@@ -79,5 +79,52 @@ __host__ __device__ inline uint64_t packed_hi(uint32_t w2) { return (uint64_t)((
 // is the no-valid-entry draw: what every sampler writes for a component the mask leaves empty.
 __host__ __device__ inline int draw_uniform(uint32_t r, int n) { return (int)(((uint64_t)r * (uint32_t)n) >> 32); }
 
+// Packed actions: a row's seven components in one uint32 bit pattern, packed [N][HW] int32
+// (include/microrts_amd.h states the same):
+//   component k's value in ACT_WBITS[k] bits from bit ACT_WOFF[k] -- the fewest bits that hold
+//   0 .. ACT_LEN[k] - 1, the fields laid end to end from bit 0 --
+//   bit ACT_WFLAG + k = component k's INVALID flag; the bits above are zero in everything the
+//   library writes and ignored by everything that reads.
+// A word stands for the dense row act_word_get gives: component k is -1 when flag k is set and
+// the field's value otherwise (a field value >= ACT_LEN[k] is out of range as the same int64 is).
+// act_word_pack puts component k into its field when it lies in [0, 2^ACT_WBITS[k]); otherwise
+// the field is 0 and the flag is set: such a component is out of range in the dense row as well,
+// so every reader treats pack(row) as it treats the row.
+constexpr int act_field_bits(int len) {
+    int b = 0;
+    while ((1 << b) < len) b++;
+    return b;
+}
+constexpr int ACT_WBITS[ACT_COMPONENTS] = {act_field_bits(ACT_LEN[0]), act_field_bits(ACT_LEN[1]), act_field_bits(ACT_LEN[2]),
+                                           act_field_bits(ACT_LEN[3]), act_field_bits(ACT_LEN[4]), act_field_bits(ACT_LEN[5]),
+                                           act_field_bits(ACT_LEN[6])};
+constexpr int act_field_off(int k) {
+    int o = 0;
+    for (int j = 0; j < k; j++) o += ACT_WBITS[j];
+    return o;
+}
+constexpr int ACT_WOFF[ACT_COMPONENTS] = {act_field_off(0), act_field_off(1), act_field_off(2), act_field_off(3),
+                                          act_field_off(4), act_field_off(5), act_field_off(6)};
+constexpr int ACT_WFLAG = act_field_off(ACT_COMPONENTS);   // the first flag bit: the fields' total width
+constexpr int ACT_WUSED = ACT_WFLAG + ACT_COMPONENTS;       // bits that carry anything
+static_assert(ACT_COMPONENTS == 7, "ACT_WBITS / ACT_WOFF list seven components");
+static_assert(ACT_WFLAG == 20 && ACT_WUSED == 27 && ACT_WUSED <= 32, "20 field bits + 7 flags in one 32-bit word");
+static_assert(ACT_WOFF[ACT_ATTACK_CELL] == 14 && ACT_WBITS[ACT_ATTACK_CELL] == 6 && ACT_WBITS[ACT_TYPE] == 3, "the documented layout");
+constexpr uint64_t ACT_WOFF_BYTES = act_pack(ACT_WOFF), ACT_WBITS_BYTES = act_pack(ACT_WBITS);
+__host__ __device__ inline int act_word_off(int k) { return (int)((ACT_WOFF_BYTES >> (8 * k)) & 0xFF); }
+__host__ __device__ inline int act_word_bits(int k) { return (int)((ACT_WBITS_BYTES >> (8 * k)) & 0xFF); }
+// component k (< ACT_COMPONENTS) of the dense row the word stands for
+__host__ __device__ inline int act_word_get(uint32_t w, int k) {
+    return ((w >> (ACT_WFLAG + k)) & 1u) ? -1 : (int)((w >> act_word_off(k)) & ((1u << act_word_bits(k)) - 1u));
+}
+__host__ __device__ inline uint32_t act_word_put(uint32_t w, int k, long long v) {
+    return (v >= 0 && v < (1ll << act_word_bits(k))) ? w | ((uint32_t)v << act_word_off(k)) : w | (1u << (ACT_WFLAG + k));
+}
+__host__ __device__ inline uint32_t act_word_pack(const int64_t* row) {
+    uint32_t w = 0;
+    for (int k = 0; k < ACT_COMPONENTS; k++) w = act_word_put(w, k, row[k]);
+    return w;
+}
+
 }  // namespace mrts
 #endif

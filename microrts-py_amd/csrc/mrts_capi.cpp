@@ -207,6 +207,9 @@ struct mrts_vec {
     // and any of the launches above that fails while masks are bound clears it.
     int mask_delta = 1;          // requested
     bool masks_synced = false;
+    // action format (mrts_set_action_format): what the steps' `actions` pointer holds.  A reader's setting:
+    // it changes no game state and is not part of the configuration fingerprint.
+    int act_packed = 0;
     // delta obs (mrts_set_obs_delta; dense obs kinds): k_step stores only the obs rows whose one-hot
     // word differs from the loaded state's, which needs every row of the step's obs buffer to be the
     // one-hot of the stored state (parked games: zeros).  The obs pointer arrives per call, so the engine
@@ -483,6 +486,14 @@ int mrts_set_mask_delta(mrts_vec *h, int32_t on) {
     return MRTS_OK;
 }
 
+int mrts_set_action_format(mrts_vec *h, int32_t format) {
+    if (!h) return fail(h, MRTS_EINVAL, "set_action_format: null handle");
+    if (format != MRTS_ACT_DENSE && format != MRTS_ACT_PACKED)
+        return fail(h, MRTS_EINVAL, "set_action_format: format must be MRTS_ACT_DENSE or MRTS_ACT_PACKED");
+    h->act_packed = format == MRTS_ACT_PACKED ? 1 : 0;
+    return MRTS_OK;
+}
+
 int mrts_set_obs_delta(mrts_vec *h, int32_t on) {
     if (!h) return fail(h, MRTS_EINVAL, "set_obs_delta: null handle");
     h->obs_delta = on ? 1 : 0;   // obs_synced_ptr stays: a dense step keeps the buffer in sync too
@@ -539,6 +550,7 @@ int mrts_get_masks_packed(mrts_vec *h, void *stream, int32_t *packed) {
 static EngineParams step_params(const mrts_vec *h, const mrts_step_io &io) {
     EngineParams p = out_params(h, io.obs);
     p.actions = io.actions;
+    p.act_packed = h->act_packed;
     p.src = io.source;
     p.raw_reward = io.raw_reward;
     p.done = io.done;
@@ -556,6 +568,8 @@ static EngineParams step_params(const mrts_vec *h, const mrts_step_io &io) {
 static bool io_ok(const mrts_step_io &io, bool weighted) {
     return io.actions && io.source && io.obs && io.raw_reward && io.done && (!weighted || (io.reward && io.done0));
 }
+// a packed-action engine reads `actions` as int32 words: 4-byte alignment is all it needs
+static bool actions_aligned(const mrts_vec *h, const mrts_step_io &io) { return !h->act_packed || ((uintptr_t)io.actions & 3u) == 0; }
 
 int mrts_get_raw_obs(mrts_vec *h, void *stream, int32_t *raw) {
     if (!bound(h) || !raw) return fail(h, MRTS_ESTATE, "get_raw_obs: workspace not bound or raw null");
@@ -632,6 +646,7 @@ static int group_check(mrts_vec *const *hs, int32_t n, const mrts_step_io *io, i
         if (!hs[i]) return group_fail(hs, i, MRTS_EINVAL, "step_group: null handle");
         if ((need_bound && !bound(hs[i])) || (io && !io_ok(io[i], io[i].reward != nullptr)))
             return group_fail(hs, i, MRTS_ESTATE, "step_group: workspace not bound or null buffer");
+        if (io && !actions_aligned(hs[i], io[i])) return group_fail(hs, i, MRTS_EINVAL, "step_group: packed action words must be 4-byte aligned");
         for (int j = 0; j < i; j++)
             if (hs[j] == hs[i]) return group_fail(hs, i, MRTS_EINVAL, "step_group: an engine listed twice");
         // int32 and float32 members only take separate launches; packed and dense obs are two formats of one
@@ -707,6 +722,7 @@ int mrts_step(mrts_vec *h, void *stream, const int64_t *actions, const int32_t *
               uint8_t *done) {
     const mrts_step_io io{actions, source, obs, raw_reward, done, nullptr, nullptr};
     if (!bound(h) || !io_ok(io, false)) return fail(h, MRTS_ESTATE, "step: workspace not bound or null buffer");
+    if (!actions_aligned(h, io)) return fail(h, MRTS_EINVAL, "step: packed action words must be 4-byte aligned");
     return step_engines(&h, 1, (hipStream_t)stream, &io, MRTS_GROUP_BOTS_FIRST, "step");
 }
 
@@ -714,6 +730,7 @@ int mrts_step_weighted(mrts_vec *h, void *stream, const int64_t *actions, const 
                        double *raw_reward, uint8_t *done, double *reward, uint8_t *done0) {
     const mrts_step_io io{actions, source, obs, raw_reward, done, reward, done0};
     if (!bound(h) || !io_ok(io, true)) return fail(h, MRTS_ESTATE, "step_weighted: workspace not bound or null buffer");
+    if (!actions_aligned(h, io)) return fail(h, MRTS_EINVAL, "step_weighted: packed action words must be 4-byte aligned");
     return step_engines(&h, 1, (hipStream_t)stream, &io, MRTS_GROUP_BOTS_FIRST, "step");
 }
 
@@ -819,6 +836,27 @@ int mrts_sample_actions_src(void *stream, const int32_t *mask, const int32_t *so
     return mrts_engine_sample_src(mask, source, n, hw, env0, seed, step, actions, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
+static bool aligned_to(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
+
+int mrts_sample_actions_src_packed(void *stream, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw, int32_t env0,
+                                   uint64_t seed, uint32_t step, int32_t *words) {
+    if (!mask || !source || !words || env0 < 0 || !sampler_rows_ok(n, hw) || !aligned_to(words, 4)) return MRTS_EINVAL;
+    return mrts_engine_sample_src_packed(mask, source, n, hw, env0, seed, step, words, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
+// The action converters (mrts_sampler.hip): rows within the samplers' bound, each side aligned to its element.
+static bool action_rows_ok(const void *actions, const void *words, int64_t rows) {
+    return actions && words && rows >= 0 && rows <= (int64_t)INT32_MAX - 256 && aligned_to(actions, 8) && aligned_to(words, 4);
+}
+int mrts_pack_actions(void *stream, const int64_t *actions, int64_t rows, int32_t *words) {
+    if (!action_rows_ok(actions, words, rows)) return MRTS_EINVAL;
+    return mrts_engine_pack_actions(actions, rows, words, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+int mrts_unpack_actions(void *stream, const int32_t *words, int64_t rows, int64_t *actions) {
+    if (!action_rows_ok(actions, words, rows)) return MRTS_EINVAL;
+    return mrts_engine_unpack_actions(words, rows, actions, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
 int mrts_sample_actions_src_group(void *stream, const mrts_sample_seg *segs, int32_t nseg, uint64_t seed, uint32_t step) {
     if (!segs || nseg < 1 || nseg > MRTS_SAMPLE_GROUP_MAX) return MRTS_EINVAL;
     for (int k = 0; k < nseg; k++) {
@@ -831,52 +869,81 @@ int mrts_sample_actions_src_group(void *stream, const mrts_sample_seg *segs, int
 
 // The action head's entry points, dense (mask + source) and packed (the words, no source),
 // over one check and one launcher each.
-static int policy_sample(int packed, void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n,
-                         int32_t hw, int32_t env0, uint64_t seed, uint32_t step, int64_t *actions, float *logprob, float *entropy) {
-    if (!logits || !mask || (!packed && !source) || !actions || !logprob || !entropy || env0 < 0 || !sampler_rows_ok(n, hw))
+// `packed`: the mask format; `apacked`: the action format (0 / 1 each: formats_ok checked the public values).
+static bool formats_ok(int32_t mask_format, int32_t action_format) {
+    return (mask_format == MRTS_MASK_DENSE || mask_format == MRTS_MASK_PACKED) &&
+           (action_format == MRTS_ACT_DENSE || action_format == MRTS_ACT_PACKED);
+}
+static bool actions_ok(int apacked, const void *actions) { return actions && ((uintptr_t)actions & (apacked ? 3u : 7u)) == 0; }
+static int policy_sample(int packed, int apacked, void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n,
+                         int32_t hw, int32_t env0, uint64_t seed, uint32_t step, void *actions, float *logprob, float *entropy) {
+    if (!logits || !mask || (!packed && !source) || !actions_ok(apacked, actions) || !logprob || !entropy || env0 < 0 || !sampler_rows_ok(n, hw))
         return MRTS_EINVAL;
-    return mrts_engine_policy_sample(packed, logits, mask, source, n, hw, env0, seed, step, actions, logprob, entropy,
+    return mrts_engine_policy_sample(packed, apacked, logits, mask, source, n, hw, env0, seed, step, actions, logprob, entropy,
                                      (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
-static int policy_evaluate(int packed, void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n,
-                           int32_t hw, const int64_t *actions, float *logprob, float *entropy) {
-    if (!logits || !mask || (!packed && !source) || !actions || !logprob || !entropy || !sampler_rows_ok(n, hw)) return MRTS_EINVAL;
-    return mrts_engine_policy_eval(packed, logits, mask, source, n, hw, actions, logprob, entropy, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
-}
-static int policy_evaluate_backward(int packed, void *stream, const float *logits, const int32_t *mask, const int32_t *source,
-                                    int32_t n, int32_t hw, const int64_t *actions, const float *grad_logprob,
-                                    const float *grad_entropy, float *grad_logits) {
-    if (!logits || !mask || (!packed && !source) || !actions || !grad_logprob || !grad_entropy || !grad_logits || !sampler_rows_ok(n, hw))
+static int policy_evaluate(int packed, int apacked, void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n,
+                           int32_t hw, const void *actions, float *logprob, float *entropy) {
+    if (!logits || !mask || (!packed && !source) || !actions_ok(apacked, actions) || !logprob || !entropy || !sampler_rows_ok(n, hw))
         return MRTS_EINVAL;
-    return mrts_engine_policy_eval_bwd(packed, logits, mask, source, n, hw, actions, grad_logprob, grad_entropy, grad_logits,
+    return mrts_engine_policy_eval(packed, apacked, logits, mask, source, n, hw, actions, logprob, entropy, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+static int policy_evaluate_backward(int packed, int apacked, void *stream, const float *logits, const int32_t *mask, const int32_t *source,
+                                    int32_t n, int32_t hw, const void *actions, const float *grad_logprob,
+                                    const float *grad_entropy, float *grad_logits) {
+    if (!logits || !mask || (!packed && !source) || !actions_ok(apacked, actions) || !grad_logprob || !grad_entropy || !grad_logits || !sampler_rows_ok(n, hw))
+        return MRTS_EINVAL;
+    return mrts_engine_policy_eval_bwd(packed, apacked, logits, mask, source, n, hw, actions, grad_logprob, grad_entropy, grad_logits,
                                        (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
 int mrts_policy_sample(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw,
                        int32_t env0, uint64_t seed, uint32_t step, int64_t *actions, float *logprob, float *entropy) {
-    return policy_sample(0, stream, logits, mask, source, n, hw, env0, seed, step, actions, logprob, entropy);
+    return policy_sample(0, 0, stream, logits, mask, source, n, hw, env0, seed, step, actions, logprob, entropy);
 }
 int mrts_policy_sample_packed(void *stream, const float *logits, const int32_t *packed, int32_t n, int32_t hw, int32_t env0,
                               uint64_t seed, uint32_t step, int64_t *actions, float *logprob, float *entropy) {
-    return policy_sample(1, stream, logits, packed, nullptr, n, hw, env0, seed, step, actions, logprob, entropy);
+    return policy_sample(1, 0, stream, logits, packed, nullptr, n, hw, env0, seed, step, actions, logprob, entropy);
 }
 int mrts_policy_evaluate(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw,
                          const int64_t *actions, float *logprob, float *entropy) {
-    return policy_evaluate(0, stream, logits, mask, source, n, hw, actions, logprob, entropy);
+    return policy_evaluate(0, 0, stream, logits, mask, source, n, hw, actions, logprob, entropy);
 }
 int mrts_policy_evaluate_packed(void *stream, const float *logits, const int32_t *packed, int32_t n, int32_t hw,
                                 const int64_t *actions, float *logprob, float *entropy) {
-    return policy_evaluate(1, stream, logits, packed, nullptr, n, hw, actions, logprob, entropy);
+    return policy_evaluate(1, 0, stream, logits, packed, nullptr, n, hw, actions, logprob, entropy);
 }
 int mrts_policy_evaluate_backward(void *stream, const float *logits, const int32_t *mask, const int32_t *source, int32_t n,
                                   int32_t hw, const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
                                   float *grad_logits) {
-    return policy_evaluate_backward(0, stream, logits, mask, source, n, hw, actions, grad_logprob, grad_entropy, grad_logits);
+    return policy_evaluate_backward(0, 0, stream, logits, mask, source, n, hw, actions, grad_logprob, grad_entropy, grad_logits);
 }
 int mrts_policy_evaluate_backward_packed(void *stream, const float *logits, const int32_t *packed, int32_t n, int32_t hw,
                                          const int64_t *actions, const float *grad_logprob, const float *grad_entropy,
                                          float *grad_logits) {
-    return policy_evaluate_backward(1, stream, logits, packed, nullptr, n, hw, actions, grad_logprob, grad_entropy, grad_logits);
+    return policy_evaluate_backward(1, 0, stream, logits, packed, nullptr, n, hw, actions, grad_logprob, grad_entropy, grad_logits);
+}
+
+// Both formats as arguments: `source` is read for dense masks only, `actions` is int64 rows or int32 words.
+int mrts_policy_sample_fmt(void *stream, const float *logits, int32_t mask_format, const int32_t *mask, const int32_t *source, int32_t n,
+                           int32_t hw, int32_t env0, uint64_t seed, uint32_t step, int32_t action_format, void *actions, float *logprob,
+                           float *entropy) {
+    if (!formats_ok(mask_format, action_format)) return MRTS_EINVAL;
+    return policy_sample(mask_format == MRTS_MASK_PACKED, action_format == MRTS_ACT_PACKED, stream, logits, mask, source, n, hw, env0, seed,
+                         step, actions, logprob, entropy);
+}
+int mrts_policy_evaluate_fmt(void *stream, const float *logits, int32_t mask_format, const int32_t *mask, const int32_t *source, int32_t n,
+                             int32_t hw, int32_t action_format, const void *actions, float *logprob, float *entropy) {
+    if (!formats_ok(mask_format, action_format)) return MRTS_EINVAL;
+    return policy_evaluate(mask_format == MRTS_MASK_PACKED, action_format == MRTS_ACT_PACKED, stream, logits, mask, source, n, hw, actions,
+                           logprob, entropy);
+}
+int mrts_policy_evaluate_backward_fmt(void *stream, const float *logits, int32_t mask_format, const int32_t *mask, const int32_t *source,
+                                      int32_t n, int32_t hw, int32_t action_format, const void *actions, const float *grad_logprob,
+                                      const float *grad_entropy, float *grad_logits) {
+    if (!formats_ok(mask_format, action_format)) return MRTS_EINVAL;
+    return policy_evaluate_backward(mask_format == MRTS_MASK_PACKED, action_format == MRTS_ACT_PACKED, stream, logits, mask, source, n, hw,
+                                    actions, grad_logprob, grad_entropy, grad_logits);
 }
 
 int mrts_pack_masks(void *stream, const int32_t *mask, const int32_t *source, int32_t n, int32_t hw, int32_t *packed) {

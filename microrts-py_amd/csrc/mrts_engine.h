@@ -111,7 +111,9 @@ struct EngineParams {
     int nsp, nsp_games, max_steps;
     int obs_kind;           // MRTS_OBS_*: what `obs` holds (the kernels' OT: int32_t, float, or mrts::PackedObs)
     int partial_obs;
-    const int64_t *actions; // [N][HW][7]
+    const int64_t *actions; // [N][HW][7], or the packed words [N][HW] int32 (act_packed)
+    int act_packed;         // MRTS_ACT_PACKED: `actions` holds one 32-bit word per row (mrts_actions.h); a
+                            // per-engine setting (mrts_set_action_format), so one grouped launch may hold both
     const int32_t *src;     // [N][HW]
     void *obs;              // [N][HW][P], or the packed words [N][HW] (MRTS_OBS_PACKED)
     double *raw_reward;     // [N][6]
@@ -178,16 +180,23 @@ hipError_t mrts_engine_sample(const int32_t *mask, int n, int hw, int env0, uint
 hipError_t mrts_engine_sample_src(const int32_t *mask, const int32_t *src, int n, int hw, int env0, uint64_t seed, uint32_t step,
                                   int64_t *act, hipStream_t s);
 hipError_t mrts_engine_sample_src_group(const mrts_sample_seg *segs, int nseg, uint64_t seed, uint32_t step, hipStream_t s);
+// k_sample_src's picks as packed action words [n][hw] (mrts_actions.h), and the converters between the
+// words and the int64 rows (rows = n * hw; 16-byte accesses on the int64 side when it is 16-byte aligned)
+hipError_t mrts_engine_sample_src_packed(const int32_t *mask, const int32_t *src, int n, int hw, int env0, uint64_t seed, uint32_t step,
+                                         int32_t *words, hipStream_t s);
+hipError_t mrts_engine_pack_actions(const int64_t *act, long long rows, int32_t *words, hipStream_t s);
+hipError_t mrts_engine_unpack_actions(const int32_t *words, long long rows, int64_t *act, hipStream_t s);
 // mrts_policy.hip: the masked action head (sample / evaluate / evaluate's backward).  packed == 0: `mask` is
 // the dense [n][hw][78] with its `src` [n][hw]; packed != 0: `mask` is the packed words [n][hw][3]
-// (mrts_actions.h) and `src` is not read.  Then the converters (rows = n * hw).
-hipError_t mrts_engine_policy_sample(int packed, const float *logits, const int32_t *mask, const int32_t *src, int n, int hw,
-                                     int env0, uint64_t seed, uint32_t step, int64_t *act, float *logprob, float *entropy,
+// (mrts_actions.h) and `src` is not read.  act_packed == 0: `act` is the int64 rows [n][hw][7]; != 0: it is
+// the packed action words [n][hw] int32.  Then the mask converters (rows = n * hw).
+hipError_t mrts_engine_policy_sample(int packed, int act_packed, const float *logits, const int32_t *mask, const int32_t *src, int n,
+                                     int hw, int env0, uint64_t seed, uint32_t step, void *act, float *logprob, float *entropy,
                                      hipStream_t s);
-hipError_t mrts_engine_policy_eval(int packed, const float *logits, const int32_t *mask, const int32_t *src, int n, int hw,
-                                   const int64_t *act, float *logprob, float *entropy, hipStream_t s);
-hipError_t mrts_engine_policy_eval_bwd(int packed, const float *logits, const int32_t *mask, const int32_t *src, int n, int hw,
-                                       const int64_t *act, const float *g_lp, const float *g_ent, float *grad, hipStream_t s);
+hipError_t mrts_engine_policy_eval(int packed, int act_packed, const float *logits, const int32_t *mask, const int32_t *src, int n,
+                                   int hw, const void *act, float *logprob, float *entropy, hipStream_t s);
+hipError_t mrts_engine_policy_eval_bwd(int packed, int act_packed, const float *logits, const int32_t *mask, const int32_t *src, int n,
+                                       int hw, const void *act, const float *g_lp, const float *g_ent, float *grad, hipStream_t s);
 hipError_t mrts_engine_pack_masks(const int32_t *mask, const int32_t *src, long long rows, int32_t *packed, hipStream_t s);
 hipError_t mrts_engine_unpack_masks(const int32_t *packed, long long rows, int32_t *mask, int32_t *src, hipStream_t s);
 // mrts_obs.hip: the converters between the packed obs words (mrts_rules.h cell_onehot) and the dense planes.

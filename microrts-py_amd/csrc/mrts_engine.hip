@@ -1342,10 +1342,17 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     // the agent's action row of cell c's idle unit (view v, owner ow): decode +
     // legality + the target claims; returns its aux word
     auto decode_row = [&](int c, int v, int ow) -> uint32_t {
-        const int64_t* ra = p.actions + ((size_t)(G.env0 + v) * HW + c) * 7;
+        const size_t row = (size_t)(G.env0 + v) * HW + c;
         int64_t r[ACT_COMPONENTS];   // all 7 components in one round trip
+        if (p.act_packed) {   // wave-uniform (an engine's setting): one word, the dense row it stands for (mrts_actions.h)
+            const uint32_t w = (uint32_t)reinterpret_cast<const int32_t*>(p.actions)[row];
 #pragma unroll
-        for (int k = 0; k < ACT_COMPONENTS; k++) r[k] = ra[k];
+            for (int k = 0; k < ACT_COMPONENTS; k++) r[k] = act_word_get(w, k);
+        } else {
+            const int64_t* ra = p.actions + row * 7;
+#pragma unroll
+            for (int k = 0; k < ACT_COMPONENTS; k++) r[k] = ra[k];
+        }
         int64_t ty = r[ACT_TYPE];
         int code = -1;
         if (ty == A_NONE) code = code_make(A_NONE, 1, 0);   // NONE(1): param = duration

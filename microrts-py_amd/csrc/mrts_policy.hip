@@ -40,6 +40,12 @@
 // the actions) are loaded and no load depends on another.  From the ballots on -- the
 // fold proper -- both forms run the same code: the results are the same bits.
 // In this unit too: the converters between the two forms (k_pack_masks, k_unpack_masks).
+//
+// Packed actions (mrts_actions.h; k_policy_*_words<PACKED>): the action format is one more
+// template parameter of the same bodies.  sample stages its rows in LDS as before and each lane
+// stores pack() of its row -- one 256-byte store per wave instead of 3.5 KB; evaluate and the
+// backward load one word per source row and lane k < 7 takes component k of the row it stands
+// for (-1 where the flag is set: forbidden like any out-of-range value).  Same arithmetic, same bits.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -89,7 +95,7 @@ struct RowRegs<true> {
 struct GroupWords {
     uint32_t w0, w1, w2;
 };
-template <Mode MODE, bool PACKED>
+template <Mode MODE, bool PACKED, bool AWORDS>
 __device__ __forceinline__ void load_row(RowRegs<PACKED>& R, size_t row, int r, const GroupWords& gw, const int32_t* __restrict__ mask,
                                          const float* __restrict__ logits, const int64_t* __restrict__ act, int lane) {
     if constexpr (PACKED) {
@@ -117,7 +123,11 @@ __device__ __forceinline__ void load_row(RowRegs<PACKED>& R, size_t row, int r, 
         R.m1 = m[c1];
         R.l1 = l[c1];
     }
-    R.a = MODE == SAMPLE ? 0 : act[row * 7 + min(lane, 6)];
+    if constexpr (AWORDS) {   // `act` is the packed action words [rows]: lane k < 7 takes component k of the row the word stands for
+        R.a = MODE == SAMPLE ? 0 : act_word_get((uint32_t) reinterpret_cast<const int32_t*>(act)[row], min(lane, 6));
+    } else {
+        R.a = MODE == SAMPLE ? 0 : act[row * 7 + min(lane, 6)];
+    }
 }
 
 // Fold one source row (wave-uniform index r of the wave's 64 rows).  SAMPLE: the picks
@@ -208,7 +218,7 @@ __device__ __forceinline__ void fold_row(const RowRegs<PACKED>& R, int r, int la
 
 // The source rows `pending` (bits of the wave's 64 rows from row0) in ascending order,
 // the next row's loads issued before the current one is folded.
-template <Mode MODE, bool PACKED>
+template <Mode MODE, bool PACKED, bool AWORDS>
 __device__ __forceinline__ void fold_rows(uint64_t pending, size_t row0, int lane, const float* __restrict__ logits,
                                           const int32_t* __restrict__ mask, const GroupWords& gw, const int64_t* __restrict__ act,
                                           WaveRow& W, const uint32_t (&r8)[8], int64_t* __restrict__ s_out, double& slp, double& sent,
@@ -217,13 +227,13 @@ __device__ __forceinline__ void fold_rows(uint64_t pending, size_t row0, int lan
     int r = __builtin_ctzll(pending);
     pending &= pending - 1ull;
     RowRegs<PACKED> cur;
-    load_row<MODE, PACKED>(cur, row0 + r, r, gw, mask, logits, act, lane);
+    load_row<MODE, PACKED, AWORDS>(cur, row0 + r, r, gw, mask, logits, act, lane);
     while (true) {
         const bool more = pending != 0;
         const int rn = more ? __builtin_ctzll(pending) : r;   // none left: a harmless re-read
         pending &= pending - 1ull;
         RowRegs<PACKED> nxt;
-        load_row<MODE, PACKED>(nxt, row0 + rn, rn, gw, mask, logits, act, lane);
+        load_row<MODE, PACKED, AWORDS>(nxt, row0 + rn, rn, gw, mask, logits, act, lane);
         fold_row<MODE, PACKED>(cur, r, lane, W, r8, s_out, slp, sent, g_lp, g_ent,
                                MODE == BWD ? grad + (row0 + r) * MRTS_MASK_CH : nullptr);
         if (!more) break;
@@ -288,7 +298,9 @@ __device__ __forceinline__ void reduce_env(double slp, double sent, float* __res
 // writes them with 16-byte stores when the env's first row is 16-byte aligned (56-byte
 // rows: an odd hw with an odd env is not), per element otherwise.
 // PACKED (the three bodies below): `mask` is packed [N][HW][3] and `src` is not read.
-template <bool PACKED>
+// AWORDS: `act` is the packed action words [N][HW] int32 (mrts_actions.h) behind the int64 pointer: sample
+// stores pack() of the staged rows, evaluate and its backward read the row a word stands for.
+template <bool PACKED, bool AWORDS>
 __device__ __forceinline__ void policy_sample(const float* __restrict__ logits, const int32_t* __restrict__ mask,
                                               const int32_t* __restrict__ src, int hw, int env0, uint64_t seed, uint32_t step,
                                               int64_t* __restrict__ act, float* __restrict__ logprob, float* __restrict__ entropy) {
@@ -310,11 +322,13 @@ __device__ __forceinline__ void policy_sample(const float* __restrict__ logits, 
             for (int k = 0; k < ACT_COMPONENTS; k++) s_out[w][lane * 7 + k] = draw_uniform(r8[k], ACT_LEN[k]);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-        fold_rows<SAMPLE, PACKED>(__ballot(in && s_raw != 0), base + c0, lane, logits, mask, gw, nullptr, s_row[w], r8, s_out[w], slp, sent,
+        fold_rows<SAMPLE, PACKED, AWORDS>(__ballot(in && s_raw != 0), base + c0, lane, logits, mask, gw, nullptr, s_row[w], r8, s_out[w], slp, sent,
                                   0.0f, 0.0f, nullptr);
         int64_t* ob = act + (base + c0) * 7;
         const int onel = rb * 7;
-        if (al16) {
+        if constexpr (AWORDS) {   // each lane packs its staged row: one coalesced 256-byte store per wave
+            if (in) reinterpret_cast<int32_t*>(act)[base + c0 + lane] = (int32_t)act_word_pack(s_out[w] + lane * 7);
+        } else if (al16) {
             const int onv = onel >> 1;
             int4* o4 = reinterpret_cast<int4*>(ob);
             const int4* s4 = reinterpret_cast<const int4*>(s_out[w]);
@@ -329,7 +343,7 @@ __device__ __forceinline__ void policy_sample(const float* __restrict__ logits, 
 }
 
 // The same inputs + the caller's actions -> logprob [N], entropy [N].
-template <bool PACKED>
+template <bool PACKED, bool AWORDS>
 __device__ __forceinline__ void policy_eval(const float* __restrict__ logits, const int32_t* __restrict__ mask,
                                             const int32_t* __restrict__ src, int hw, const int64_t* __restrict__ act,
                                             float* __restrict__ logprob, float* __restrict__ entropy) {
@@ -342,7 +356,7 @@ __device__ __forceinline__ void policy_eval(const float* __restrict__ logits, co
         const int rb = min(64, hw - c0);
         GroupWords gw;
         const int s_raw = group_source<PACKED>(mask, src, base + c0, rb, lane, gw);
-        fold_rows<EVAL, PACKED>(__ballot(lane < rb && s_raw != 0), base + c0, lane, logits, mask, gw, act, s_row[w], r8, nullptr, slp, sent,
+        fold_rows<EVAL, PACKED, AWORDS>(__ballot(lane < rb && s_raw != 0), base + c0, lane, logits, mask, gw, act, s_row[w], r8, nullptr, slp, sent,
                                 0.0f, 0.0f, nullptr);
     }
     reduce_env(slp, sent, logprob, entropy, e);
@@ -352,7 +366,7 @@ __device__ __forceinline__ void policy_eval(const float* __restrict__ logits, co
 // workgroup fills its env's rows with +0.0f (16-byte stores when the env's first row
 // is 16-byte aligned -- 312-byte rows: an odd hw with an odd env is not -- per element
 // otherwise), then the waves store the source rows' valid channels over the fill.
-template <bool PACKED>
+template <bool PACKED, bool AWORDS>
 __device__ __forceinline__ void policy_eval_bwd(const float* __restrict__ logits, const int32_t* __restrict__ mask,
                                                 const int32_t* __restrict__ src, int hw, const int64_t* __restrict__ act,
                                                 const float* __restrict__ g_lp, const float* __restrict__ g_ent,
@@ -378,7 +392,7 @@ __device__ __forceinline__ void policy_eval_bwd(const float* __restrict__ logits
         const int rb = min(64, hw - c0);
         GroupWords gw;
         const int s_raw = group_source<PACKED>(mask, src, base + c0, rb, lane, gw);
-        fold_rows<BWD, PACKED>(__ballot(lane < rb && s_raw != 0), base + c0, lane, logits, mask, gw, act, s_row[w], r8, nullptr, slp, sent,
+        fold_rows<BWD, PACKED, AWORDS>(__ballot(lane < rb && s_raw != 0), base + c0, lane, logits, mask, gw, act, s_row[w], r8, nullptr, slp, sent,
                                glp, gent, grad);
     }
 }
@@ -388,33 +402,55 @@ __global__ __launch_bounds__(PT) void k_policy_sample(const float* __restrict__ 
                                                       const int32_t* __restrict__ src, int hw, int env0, uint64_t seed, uint32_t step,
                                                       int64_t* __restrict__ act, float* __restrict__ logprob,
                                                       float* __restrict__ entropy) {
-    policy_sample<false>(logits, mask, src, hw, env0, seed, step, act, logprob, entropy);
+    policy_sample<false, false>(logits, mask, src, hw, env0, seed, step, act, logprob, entropy);
 }
 __global__ __launch_bounds__(PT) void k_policy_eval(const float* __restrict__ logits, const int32_t* __restrict__ mask,
                                                     const int32_t* __restrict__ src, int hw, const int64_t* __restrict__ act,
                                                     float* __restrict__ logprob, float* __restrict__ entropy) {
-    policy_eval<false>(logits, mask, src, hw, act, logprob, entropy);
+    policy_eval<false, false>(logits, mask, src, hw, act, logprob, entropy);
 }
 __global__ __launch_bounds__(PT) void k_policy_eval_bwd(const float* __restrict__ logits, const int32_t* __restrict__ mask,
                                                         const int32_t* __restrict__ src, int hw, const int64_t* __restrict__ act,
                                                         const float* __restrict__ g_lp, const float* __restrict__ g_ent,
                                                         float* __restrict__ grad) {
-    policy_eval_bwd<false>(logits, mask, src, hw, act, g_lp, g_ent, grad);
+    policy_eval_bwd<false, false>(logits, mask, src, hw, act, g_lp, g_ent, grad);
 }
 __global__ __launch_bounds__(PT) void k_policy_sample_packed(const float* __restrict__ logits, const int32_t* __restrict__ packed, int hw,
                                                              int env0, uint64_t seed, uint32_t step, int64_t* __restrict__ act,
                                                              float* __restrict__ logprob, float* __restrict__ entropy) {
-    policy_sample<true>(logits, packed, nullptr, hw, env0, seed, step, act, logprob, entropy);
+    policy_sample<true, false>(logits, packed, nullptr, hw, env0, seed, step, act, logprob, entropy);
 }
 __global__ __launch_bounds__(PT) void k_policy_eval_packed(const float* __restrict__ logits, const int32_t* __restrict__ packed, int hw,
                                                            const int64_t* __restrict__ act, float* __restrict__ logprob,
                                                            float* __restrict__ entropy) {
-    policy_eval<true>(logits, packed, nullptr, hw, act, logprob, entropy);
+    policy_eval<true, false>(logits, packed, nullptr, hw, act, logprob, entropy);
 }
 __global__ __launch_bounds__(PT) void k_policy_eval_bwd_packed(const float* __restrict__ logits, const int32_t* __restrict__ packed, int hw,
                                                                const int64_t* __restrict__ act, const float* __restrict__ g_lp,
                                                                const float* __restrict__ g_ent, float* __restrict__ grad) {
-    policy_eval_bwd<true>(logits, packed, nullptr, hw, act, g_lp, g_ent, grad);
+    policy_eval_bwd<true, false>(logits, packed, nullptr, hw, act, g_lp, g_ent, grad);
+}
+
+// The same three over packed action words, either mask format (PACKED: `mask` is the packed masks, `src` unused).
+template <bool PACKED>
+__global__ __launch_bounds__(PT) void k_policy_sample_words(const float* __restrict__ logits, const int32_t* __restrict__ mask,
+                                                            const int32_t* __restrict__ src, int hw, int env0, uint64_t seed, uint32_t step,
+                                                            int32_t* __restrict__ words, float* __restrict__ logprob,
+                                                            float* __restrict__ entropy) {
+    policy_sample<PACKED, true>(logits, mask, src, hw, env0, seed, step, reinterpret_cast<int64_t*>(words), logprob, entropy);
+}
+template <bool PACKED>
+__global__ __launch_bounds__(PT) void k_policy_eval_words(const float* __restrict__ logits, const int32_t* __restrict__ mask,
+                                                          const int32_t* __restrict__ src, int hw, const int32_t* __restrict__ words,
+                                                          float* __restrict__ logprob, float* __restrict__ entropy) {
+    policy_eval<PACKED, true>(logits, mask, src, hw, reinterpret_cast<const int64_t*>(words), logprob, entropy);
+}
+template <bool PACKED>
+__global__ __launch_bounds__(PT) void k_policy_eval_bwd_words(const float* __restrict__ logits, const int32_t* __restrict__ mask,
+                                                              const int32_t* __restrict__ src, int hw, const int32_t* __restrict__ words,
+                                                              const float* __restrict__ g_lp, const float* __restrict__ g_ent,
+                                                              float* __restrict__ grad) {
+    policy_eval_bwd<PACKED, true>(logits, mask, src, hw, reinterpret_cast<const int64_t*>(words), g_lp, g_ent, grad);
 }
 
 // ---------------------------------------------------------------------------
@@ -499,28 +535,43 @@ __global__ __launch_bounds__(PT) void k_unpack_masks(const int32_t* __restrict__
 }  // namespace mrts
 
 // The launchers take the caller's stream, allocate nothing and synchronise nothing.
-// `packed` picks the packed-mask kernel, which takes no src.
+// `packed` picks the packed-mask kernel, which takes no src; `act_packed` the kernel over packed action words.
 extern "C" {
 using namespace mrts::policy;
-hipError_t mrts_engine_policy_sample(int packed, const float* logits, const int32_t* mask, const int32_t* src, int n, int hw, int env0,
-                                     uint64_t seed, uint32_t step, int64_t* act, float* logprob, float* entropy, hipStream_t s) {
+hipError_t mrts_engine_policy_sample(int packed, int act_packed, const float* logits, const int32_t* mask, const int32_t* src, int n, int hw,
+                                     int env0, uint64_t seed, uint32_t step, void* act, float* logprob, float* entropy, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    if (packed) hipLaunchKernelGGL(k_policy_sample_packed, dim3((unsigned)n), dim3(PT), 0, s, logits, mask, hw, env0, seed, step, act, logprob, entropy);
-    else hipLaunchKernelGGL(k_policy_sample, dim3((unsigned)n), dim3(PT), 0, s, logits, mask, src, hw, env0, seed, step, act, logprob, entropy);
+    const dim3 g((unsigned)n), b(PT);
+    int64_t* const rows = static_cast<int64_t*>(act);
+    int32_t* const words = static_cast<int32_t*>(act);
+    if (act_packed && packed) hipLaunchKernelGGL(k_policy_sample_words<true>, g, b, 0, s, logits, mask, src, hw, env0, seed, step, words, logprob, entropy);
+    else if (act_packed) hipLaunchKernelGGL(k_policy_sample_words<false>, g, b, 0, s, logits, mask, src, hw, env0, seed, step, words, logprob, entropy);
+    else if (packed) hipLaunchKernelGGL(k_policy_sample_packed, g, b, 0, s, logits, mask, hw, env0, seed, step, rows, logprob, entropy);
+    else hipLaunchKernelGGL(k_policy_sample, g, b, 0, s, logits, mask, src, hw, env0, seed, step, rows, logprob, entropy);
     return hipGetLastError();
 }
-hipError_t mrts_engine_policy_eval(int packed, const float* logits, const int32_t* mask, const int32_t* src, int n, int hw,
-                                   const int64_t* act, float* logprob, float* entropy, hipStream_t s) {
+hipError_t mrts_engine_policy_eval(int packed, int act_packed, const float* logits, const int32_t* mask, const int32_t* src, int n, int hw,
+                                   const void* act, float* logprob, float* entropy, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    if (packed) hipLaunchKernelGGL(k_policy_eval_packed, dim3((unsigned)n), dim3(PT), 0, s, logits, mask, hw, act, logprob, entropy);
-    else hipLaunchKernelGGL(k_policy_eval, dim3((unsigned)n), dim3(PT), 0, s, logits, mask, src, hw, act, logprob, entropy);
+    const dim3 g((unsigned)n), b(PT);
+    const int64_t* const rows = static_cast<const int64_t*>(act);
+    const int32_t* const words = static_cast<const int32_t*>(act);
+    if (act_packed && packed) hipLaunchKernelGGL(k_policy_eval_words<true>, g, b, 0, s, logits, mask, src, hw, words, logprob, entropy);
+    else if (act_packed) hipLaunchKernelGGL(k_policy_eval_words<false>, g, b, 0, s, logits, mask, src, hw, words, logprob, entropy);
+    else if (packed) hipLaunchKernelGGL(k_policy_eval_packed, g, b, 0, s, logits, mask, hw, rows, logprob, entropy);
+    else hipLaunchKernelGGL(k_policy_eval, g, b, 0, s, logits, mask, src, hw, rows, logprob, entropy);
     return hipGetLastError();
 }
-hipError_t mrts_engine_policy_eval_bwd(int packed, const float* logits, const int32_t* mask, const int32_t* src, int n, int hw,
-                                       const int64_t* act, const float* g_lp, const float* g_ent, float* grad, hipStream_t s) {
+hipError_t mrts_engine_policy_eval_bwd(int packed, int act_packed, const float* logits, const int32_t* mask, const int32_t* src, int n, int hw,
+                                       const void* act, const float* g_lp, const float* g_ent, float* grad, hipStream_t s) {
     if (n == 0) return hipSuccess;
-    if (packed) hipLaunchKernelGGL(k_policy_eval_bwd_packed, dim3((unsigned)n), dim3(PT), 0, s, logits, mask, hw, act, g_lp, g_ent, grad);
-    else hipLaunchKernelGGL(k_policy_eval_bwd, dim3((unsigned)n), dim3(PT), 0, s, logits, mask, src, hw, act, g_lp, g_ent, grad);
+    const dim3 g((unsigned)n), b(PT);
+    const int64_t* const rows = static_cast<const int64_t*>(act);
+    const int32_t* const words = static_cast<const int32_t*>(act);
+    if (act_packed && packed) hipLaunchKernelGGL(k_policy_eval_bwd_words<true>, g, b, 0, s, logits, mask, src, hw, words, g_lp, g_ent, grad);
+    else if (act_packed) hipLaunchKernelGGL(k_policy_eval_bwd_words<false>, g, b, 0, s, logits, mask, src, hw, words, g_lp, g_ent, grad);
+    else if (packed) hipLaunchKernelGGL(k_policy_eval_bwd_packed, g, b, 0, s, logits, mask, hw, rows, g_lp, g_ent, grad);
+    else hipLaunchKernelGGL(k_policy_eval_bwd, g, b, 0, s, logits, mask, src, hw, rows, g_lp, g_ent, grad);
     return hipGetLastError();
 }
 // rows = n * hw >= 1 (mrts_capi.cpp: within the samplers' row bound, so the grid is below 2^23)

@@ -1,5 +1,6 @@
-// mrts_sampler.hip -- the stand-in policy's samplers (mrts_sample_actions, _src,
-// _src_group): three kernels and their launchers.  They share the Philox stream and the
+// mrts_sampler.hip -- the stand-in policy's samplers (mrts_sample_actions, _src, _src_packed,
+// _src_group) and the converters between the int64 action rows and the packed action words:
+// the kernels and their launchers.  They share the Philox stream and the
 // action-row layout with the masked action head, and nothing with the game step.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -167,9 +168,12 @@ __global__ __launch_bounds__(64 * SWAVES) void k_sample(const int32_t* __restric
 constexpr int SR_WAVES = 4;
 constexpr int SRC_ROWS = 4;   // source rows per round trip (8 and 16 measured slower, profiles/r04_ab/r04v)
 // one block's 4 x 64 rows of one batch (k_sample_src: block = blockIdx.x; the grouped
-// launch: the block's index inside its segment)
+// launch: the block's index inside its segment).  WORDS (k_sample_src_packed): the same picks
+// as packed action words (mrts_actions.h), `act` is int32 [rows] -- each lane packs its row in
+// registers and the wave makes one coalesced 256-byte store; no LDS staging (s_out unused).
+template <bool WORDS>
 __device__ __forceinline__ void sample_src_block(const int32_t* __restrict__ mask, const int32_t* __restrict__ src, int n, int hw,
-                                                 int env0, uint64_t seed, uint32_t step, int64_t* __restrict__ act, long long blk,
+                                                 int env0, uint64_t seed, uint32_t step, void* __restrict__ act_out, long long blk,
                                                  int64_t (*s_out)[64 * 7]) {
     const int w = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const long long rows = (long long)n * hw;
@@ -211,6 +215,16 @@ __device__ __forceinline__ void sample_src_block(const int32_t* __restrict__ mas
             if (lane == r[k]) { lo = b0; hi = b1; }
         }
     }
+    if constexpr (WORDS) {
+        if (in) {
+            int64_t o[ACT_COMPONENTS];
+            select_row(lo, hi, r8, o);
+            // non-temporal like the dense rows: k_step reads ~2 % of the words back
+            __builtin_nontemporal_store((int32_t)act_word_pack(o), static_cast<int32_t*>(act_out) + row0 + lane);
+        }
+        return;
+    }
+    int64_t* const act = static_cast<int64_t*>(act_out);
     if (in) select_row(lo, hi, r8, s_out[w] + lane * 7);
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     int64_t* ob = act + row0 * 7;   // 16-B aligned: 64 * 56 B per wave
@@ -228,7 +242,12 @@ __global__ __launch_bounds__(64 * SR_WAVES) void k_sample_src(const int32_t* __r
                                                            int hw, int env0, uint64_t seed, uint32_t step,
                                                            int64_t* __restrict__ act) {
     __shared__ __attribute__((aligned(16))) int64_t s_out[SR_WAVES][64 * 7];
-    sample_src_block(mask, src, n, hw, env0, seed, step, act, blockIdx.x, s_out);
+    sample_src_block<false>(mask, src, n, hw, env0, seed, step, act, blockIdx.x, s_out);
+}
+__global__ __launch_bounds__(64 * SR_WAVES) void k_sample_src_packed(const int32_t* __restrict__ mask, const int32_t* __restrict__ src,
+                                                                  int n, int hw, int env0, uint64_t seed, uint32_t step,
+                                                                  int32_t* __restrict__ words) {
+    sample_src_block<true>(mask, src, n, hw, env0, seed, step, words, blockIdx.x, nullptr);
 }
 // Several batches (a mixed batch's size buckets) in one launch: segment k owns blocks
 // [end[k-1], end[k]); a block finds its segment with a scalar scan of the table.
@@ -249,7 +268,58 @@ __global__ __launch_bounds__(64 * SR_WAVES) void k_sample_src_group(const Sample
     int k = 0;
     while (k + 1 < g.nseg && b >= g.end[k]) k++;
     const SampleSeg& sg = g.seg[k];
-    sample_src_block(sg.mask, sg.src, sg.n, sg.hw, sg.env0, seed, step, sg.act, b - (k ? g.end[k - 1] : 0), s_out);
+    sample_src_block<false>(sg.mask, sg.src, sg.n, sg.hw, sg.env0, seed, step, sg.act, b - (k ? g.end[k - 1] : 0), s_out);
+}
+
+// ---------------------------------------------------------------------------
+// Converters between the int64 action rows [rows][7] and the packed words [rows] (mrts_actions.h),
+// over flat rows.  The int64 side is 56 bytes a row: a workgroup's AC_ROWS rows are 896 16-byte
+// chunks, moved coalesced through LDS when the int64 pointer is 16-byte aligned (then every
+// workgroup's slice is), per element otherwise.
+constexpr int AC_ROWS = 256;   // rows per workgroup, one lane each on the word side
+static_assert(AC_ROWS * ACT_COMPONENTS % 2 == 0, "a workgroup's rows are whole 16-byte chunks");
+
+// act [rows][7] i64 -> words [rows].  Eight lanes' worth of loads per row either way (the row is
+// read whole); the word store is one coalesced pass.
+__global__ __launch_bounds__(AC_ROWS) void k_pack_actions(const int64_t* __restrict__ act, long long rows, int32_t* __restrict__ words) {
+    __shared__ __attribute__((aligned(16))) int64_t s_a[AC_ROWS * ACT_COMPONENTS];
+    const long long row0 = (long long)blockIdx.x * AC_ROWS;
+    const int nr = (int)min((long long)AC_ROWS, rows - row0);
+    const int nel = nr * ACT_COMPONENTS;
+    const int64_t* in = act + row0 * ACT_COMPONENTS;
+    if (((uintptr_t)act & 15u) == 0) {
+        const v4i* i4 = reinterpret_cast<const v4i*>(in);
+        v4i* s4 = reinterpret_cast<v4i*>(s_a);
+        for (int k = threadIdx.x; k < nel / 2; k += AC_ROWS) s4[k] = __builtin_nontemporal_load(i4 + k);
+        if ((nel & 1) && threadIdx.x == 0) s_a[nel - 1] = in[nel - 1];
+    } else {
+        for (int k = threadIdx.x; k < nel; k += AC_ROWS) s_a[k] = in[k];
+    }
+    __syncthreads();
+    if ((int)threadIdx.x < nr) words[row0 + threadIdx.x] = (int32_t)act_word_pack(s_a + threadIdx.x * ACT_COMPONENTS);
+}
+
+// words [rows] -> act [rows][7] i64: every element written, -1 where the component's flag is set.
+__global__ __launch_bounds__(AC_ROWS) void k_unpack_actions(const int32_t* __restrict__ words, long long rows, int64_t* __restrict__ act) {
+    __shared__ __attribute__((aligned(16))) int64_t s_a[AC_ROWS * ACT_COMPONENTS];
+    const long long row0 = (long long)blockIdx.x * AC_ROWS;
+    const int nr = (int)min((long long)AC_ROWS, rows - row0);
+    const int nel = nr * ACT_COMPONENTS;
+    if ((int)threadIdx.x < nr) {
+        const uint32_t w = (uint32_t)words[row0 + threadIdx.x];
+#pragma unroll
+        for (int k = 0; k < ACT_COMPONENTS; k++) s_a[threadIdx.x * ACT_COMPONENTS + k] = act_word_get(w, k);
+    }
+    __syncthreads();
+    int64_t* out = act + row0 * ACT_COMPONENTS;
+    if (((uintptr_t)act & 15u) == 0) {
+        v4i* o4 = reinterpret_cast<v4i*>(out);
+        const v4i* s4 = reinterpret_cast<const v4i*>(s_a);
+        for (int k = threadIdx.x; k < nel / 2; k += AC_ROWS) o4[k] = s4[k];
+        if ((nel & 1) && threadIdx.x == 0) out[nel - 1] = s_a[nel - 1];
+    } else {
+        for (int k = threadIdx.x; k < nel; k += AC_ROWS) out[k] = s_a[k];
+    }
 }
 
 }  // namespace mrts
@@ -272,6 +342,26 @@ hipError_t mrts_engine_sample_src(const int32_t* mask, const int32_t* src, int n
     if (rows == 0) return hipSuccess;
     const long long blocks = (rows + 64 * mrts::SR_WAVES - 1) / (64 * mrts::SR_WAVES);
     hipLaunchKernelGGL(mrts::k_sample_src, dim3((unsigned)blocks), dim3(64 * mrts::SR_WAVES), 0, s, mask, src, n, hw, env0, seed, step, act);
+    return hipGetLastError();
+}
+hipError_t mrts_engine_sample_src_packed(const int32_t* mask, const int32_t* src, int n, int hw, int env0, uint64_t seed, uint32_t step,
+                                         int32_t* words, hipStream_t s) {
+    const long long rows = (long long)n * hw;
+    if (rows == 0) return hipSuccess;
+    const long long blocks = (rows + 64 * mrts::SR_WAVES - 1) / (64 * mrts::SR_WAVES);
+    hipLaunchKernelGGL(mrts::k_sample_src_packed, dim3((unsigned)blocks), dim3(64 * mrts::SR_WAVES), 0, s, mask, src, n, hw, env0, seed, step,
+                       words);
+    return hipGetLastError();
+}
+// rows within the samplers' row bound (mrts_capi.cpp): the grid is below 2^23
+hipError_t mrts_engine_pack_actions(const int64_t* act, long long rows, int32_t* words, hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(mrts::k_pack_actions, dim3((unsigned)((rows + mrts::AC_ROWS - 1) / mrts::AC_ROWS)), dim3(mrts::AC_ROWS), 0, s, act, rows, words);
+    return hipGetLastError();
+}
+hipError_t mrts_engine_unpack_actions(const int32_t* words, long long rows, int64_t* act, hipStream_t s) {
+    if (rows == 0) return hipSuccess;
+    hipLaunchKernelGGL(mrts::k_unpack_actions, dim3((unsigned)((rows + mrts::AC_ROWS - 1) / mrts::AC_ROWS)), dim3(mrts::AC_ROWS), 0, s, words, rows, act);
     return hipGetLastError();
 }
 hipError_t mrts_engine_sample_src_group(const mrts_sample_seg* segs, int nseg, uint64_t seed, uint32_t step, hipStream_t s) {

@@ -17,6 +17,8 @@ MRTS_OBS_INT32 = 0
 MRTS_OBS_FLOAT32 = 1
 MRTS_OBS_PACKED = 2
 MRTS_ELEM_INT32, MRTS_ELEM_FLOAT32, MRTS_ELEM_FLOAT16, MRTS_ELEM_BFLOAT16 = 0, 1, 2, 3
+MRTS_ACT_DENSE, MRTS_ACT_PACKED = 0, 1
+MRTS_MASK_DENSE, MRTS_MASK_PACKED = 0, 1
 MRTS_GAME_STATS = 6
 ERROR_NAMES = {-1: "EINVAL", -2: "EIO", -3: "EHIP", -4: "ENOTIMPL", -5: "ESTATE"}
 
@@ -122,6 +124,16 @@ SIGNATURES = {
                                                  ctypes.c_uint32, P, P, P]),
     "mrts_policy_evaluate_packed": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P]),
     "mrts_policy_evaluate_backward_packed": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, P, P, P, P]),
+    "mrts_set_action_format": (ctypes.c_int, [P, ctypes.c_int32]),
+    "mrts_sample_actions_src_packed": (ctypes.c_int, [P, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, ctypes.c_uint64,
+                                                      ctypes.c_uint32, P]),
+    "mrts_pack_actions": (ctypes.c_int, [P, P, ctypes.c_int64, P]),
+    "mrts_unpack_actions": (ctypes.c_int, [P, P, ctypes.c_int64, P]),
+    "mrts_policy_sample_fmt": (ctypes.c_int, [P, P, ctypes.c_int32, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                              ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int32, P, P, P]),
+    "mrts_policy_evaluate_fmt": (ctypes.c_int, [P, P, ctypes.c_int32, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P, P, P]),
+    "mrts_policy_evaluate_backward_fmt": (ctypes.c_int, [P, P, ctypes.c_int32, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
+                                                         P, P, P, P]),
     "mrts_game_stats": (ctypes.c_int, [P, P, P]),
     "mrts_bind_mask_outputs": (ctypes.c_int, [P, P, P]),
     "mrts_set_bot_fusion": (ctypes.c_int, [P, ctypes.c_int32]),

@@ -205,6 +205,7 @@ class MicroRTSGridModeVecEnv:
         obs_delta=None,
         game_offset=0,
         obs_format="dense",
+        action_format="dense",
         _ai1s=None,
         _extra_maps=(),
     ):
@@ -215,6 +216,14 @@ class MicroRTSGridModeVecEnv:
         on the numpy contract) and obs_dtype must be None or torch.int32.
         observation_space describes the dense obs either way;
         gym_microrts.packed_obs.unpack_obs turns the words into planes.
+
+        action_format: "dense" -- step() takes the reference's action rows, N*H*W*7 values -- or
+        "packed": step() takes one 32-bit word per cell, [N, H*W] or [N, H, W] int32
+        (include/microrts_amd.h "Packed actions"; gym_microrts.packed_actions converts,
+        policy_head.sample(..., action_format="packed") writes them): a contiguous device
+        tensor is read in place, any other tensor or a numpy array is copied, a numpy array
+        through page-locked staging at 4 bytes a cell.  The game played is the one the
+        unpacked rows play.  action_space describes the dense rows either way.
 
         mask_delta (eager masks only; None = on, unless the environment variable
         MICRORTS_AMD_MASK_DELTA=0): step() stores only the mask rows that can differ
@@ -302,6 +311,9 @@ class MicroRTSGridModeVecEnv:
             raise ValueError(f"obs_format must be 'dense' or 'packed', not {obs_format!r}")
         self.obs_format = obs_format
         packed_obs = obs_format == "packed"
+        if action_format not in ("dense", "packed"):
+            raise ValueError(f"action_format must be 'dense' or 'packed', not {action_format!r}")
+        self.action_format = action_format
         if packed_obs:
             if obs_dtype not in (None, torch.int32):
                 raise ValueError("obs_format='packed' holds int32 words: obs_dtype must be None or torch.int32")
@@ -338,7 +350,10 @@ class MicroRTSGridModeVecEnv:
             self._src = torch.zeros((self.num_envs, hw), dtype=torch.int32, device=self.device)
             self._raw = torch.zeros((self.num_envs, 6), dtype=torch.float64, device=self.device)
             self._done = torch.zeros((self.num_envs, 6), dtype=torch.uint8, device=self.device)
-            self._actions = torch.zeros((self.num_envs, hw, 7), dtype=torch.int64, device=self.device)
+            if action_format == "packed":   # one word per cell; the zero word is the dense buffer's all-zero row
+                self._actions = torch.zeros((self.num_envs, hw), dtype=torch.int32, device=self.device)
+            else:
+                self._actions = torch.zeros((self.num_envs, hw, 7), dtype=torch.int64, device=self.device)
             self._rew = torch.zeros((self.num_envs,), dtype=torch.float64, device=self.device)
             self._done0 = torch.zeros((self.num_envs,), dtype=torch.bool, device=self.device)
         _native.check(_native.lib().mrts_bind_workspace(self._h, self._ws.data_ptr(), self._stream()), self._h, "bind_workspace")
@@ -355,6 +370,8 @@ class MicroRTSGridModeVecEnv:
         # the same pass (mrts_set_bot_fusion; outputs identical either way)
         self.bot_fusion = bool(bot_fusion)
         _native.check(_native.lib().mrts_set_bot_fusion(self._h, int(self.bot_fusion)), self._h, "set_bot_fusion")
+        fmt = _native.MRTS_ACT_PACKED if action_format == "packed" else _native.MRTS_ACT_DENSE
+        _native.check(_native.lib().mrts_set_action_format(self._h, fmt), self._h, "set_action_format")
         # delta masks: a step stores only the mask rows that can have changed (mrts_set_mask_delta)
         if mask_delta is None:
             mask_delta = os.environ.get("MICRORTS_AMD_MASK_DELTA", "1").strip() != "0"
@@ -380,7 +397,7 @@ class MicroRTSGridModeVecEnv:
         self._mask_fresh = False   # _mask / _src hold getMasks(0) of the current state
         self._packed = None        # get_action_mask_packed()'s device buffer, allocated at its first call
         self._pool = None          # numpy contract: page-locked output arrays (HostArrayPool)
-        self._act_stage = None     # host actions: page-locked int64 staging buffer
+        self._act_stage = None     # host actions: page-locked staging buffer (int64 rows, or int32 words when packed)
         self._act_copied = None    # event after the staging buffer's last H2D copy (reused only once it fired)
         self._act_src = None       # a caller's page-locked action array being copied (kept alive until step_wait's sync)
         self._mask_prefetch = None # numpy contract: host masks of the current state, copied in step_wait's sync
@@ -493,18 +510,38 @@ class MicroRTSGridModeVecEnv:
     def source_unit_mask(self):
         return self._src.cpu().numpy() if self._host_outputs else self._src
 
+    def _action_shapes(self, got):
+        n, hw = self.num_envs, self.height * self.width
+        return (f"an action_format={self.action_format!r} env takes "
+                + (f"packed words [N, HW] = {(n, hw)} int32" if self.action_format == "packed"
+                   else f"action rows [N, HW, 7] = {(n, hw, 7)} (int64)")
+                + ", not " + got + "; the other format is "
+                + (f"action rows [N, HW, 7] = {(n, hw, 7)} int64" if self.action_format == "packed"
+                   else f"packed words [N, HW] = {(n, hw)} int32")
+                + " (gym_microrts.packed_actions converts)")
+
     def step_async(self, actions):
-        """vec_env.py:968-984: actions (N, H*W*7) (or any shape with N*H*W*7 elements)."""
+        """vec_env.py:968-984: actions (N, H*W*7) (or any shape with N*H*W*7 elements); with
+        action_format="packed", int32 words of N*H*W elements."""
         hw = self.height * self.width
+        words = self.action_format == "packed"
+        shape = tuple(self._actions.shape)
+        tdt, ndt = (torch.int32, np.int32) if words else (torch.int64, np.int64)
         if isinstance(actions, torch.Tensor):
-            a = actions.reshape(self.num_envs, hw, 7)
-            if a.device == self.device and a.dtype == torch.int64 and a.is_contiguous():
+            if actions.numel() != self._actions.numel() or (words and actions.dtype != torch.int32):
+                if words or actions.numel() == self.num_envs * hw:   # the other format's dtype or element count
+                    raise ValueError(self._action_shapes(f"{actions.dtype} {tuple(actions.shape)}"))
+            a = actions.reshape(shape)
+            if a.device == self.device and a.dtype == tdt and a.is_contiguous():
                 self._actions_in = a
                 return
             self._actions.copy_(a)
         else:
             a = np.asarray(actions)
-            if self.contract != "tensors" and a.dtype == np.int64 and a.size == self._actions.numel() and a.flags.c_contiguous:
+            if a.size != self._actions.numel() or (words and a.dtype != np.int32):
+                if words or a.size == self.num_envs * hw:
+                    raise ValueError(self._action_shapes(f"{a.dtype} {a.shape}"))
+            if self.contract != "tensors" and a.dtype == ndt and a.size == self._actions.numel() and a.flags.c_contiguous:
                 t = torch.from_numpy(a.reshape(-1))
                 if t.is_pinned():
                     # the caller's array is page-locked already (e.g. a view of a pinned
@@ -515,9 +552,9 @@ class MicroRTSGridModeVecEnv:
                     self._act_src = t
                     self._actions_in = self._actions
                     return
-            a = a.reshape(self.num_envs, hw, 7)
+            a = a.reshape(shape)
             if self._act_stage is None:
-                self._act_stage = torch.empty(tuple(self._actions.shape), dtype=torch.int64, pin_memory=True)
+                self._act_stage = torch.empty(shape, dtype=tdt, pin_memory=True)
                 self._act_copied = torch.cuda.Event()
             else:
                 # the previous step's DMA may still be queued (the tensor contract
@@ -880,7 +917,11 @@ class MicroRTSGridModeSharedMemVecEnv(MicroRTSGridModeVecEnv):
         cycle_maps=[],
         *,
         device=None,
+        action_format="dense",
     ):
+        if action_format != "dense":
+            raise ValueError("MicroRTSGridModeSharedMemVecEnv has the reference's own int32 action buffer [N, H*W, 7]: "
+                             f"action_format={action_format!r} is not available here (use MicroRTSGridModeVecEnv)")
         if len(map_paths) > 1 and len(set(map_paths)) > 1:
             raise ValueError("Mem shared environment requires all games to be played on the same map.")
         super().__init__(num_selfplay_envs, num_bot_envs, partial_obs=partial_obs, max_steps=max_steps,
@@ -935,7 +976,7 @@ class MicroRTSMixedMapVecEnv:
       mask = env.get_action_mask()             # list over buckets
       obs, rew, done, infos = env.step(actions)  # actions: list over buckets
 
-    Keyword arguments (mask_delta, obs_delta and obs_format among them) go to every bucket's engine.
+    Keyword arguments (mask_delta, obs_delta, obs_format and action_format among them) go to every bucket's engine.
     """
 
     def __init__(self, buckets, concurrent=False, group_policy="default", **common):
@@ -1080,8 +1121,9 @@ class MicroRTSSizeCyclingVecEnv:
 
     def __init__(self, num_selfplay_envs, num_bot_envs, ai2s=[], map_paths=["maps/16x16/basesWorkers16x16.xml"], cycle_maps=[],
                  max_steps=2000, partial_obs=False, reward_weight=np.array([0.0, 1.0, 0.0, 0.0, 0.0, 5.0]), device=None,
-                 obs_dtype=None, mask_delta=None, obs_format="dense", obs_delta=None):
+                 obs_dtype=None, mask_delta=None, obs_format="dense", obs_delta=None, action_format="dense"):
         self.num_selfplay_envs, self.num_bot_envs = num_selfplay_envs, num_bot_envs
+        self.action_format = action_format   # every size engine's: step() entries [N, H_i*W_i] int32 words when "packed"
         self.obs_format = obs_format   # every size engine's (MicroRTSGridModeVecEnv: obs entries [N, H_i, W_i] int32 when "packed")
         self.num_envs = num_selfplay_envs + num_bot_envs
         root = os.path.join(gym_microrts.__path__[0], "microrts")
@@ -1104,7 +1146,7 @@ class MicroRTSSizeCyclingVecEnv:
             self.envs.append(MicroRTSGridModeVecEnv(num_selfplay_envs, num_bot_envs, partial_obs=partial_obs, max_steps=max_steps,
                                                     ai2s=ai2s, map_paths=maps_i, reward_weight=reward_weight, device=device,
                                                     return_tensors=True, obs_dtype=obs_dtype, mask_delta=mask_delta, obs_delta=obs_delta,
-                                                    obs_format=obs_format, _extra_maps=own))
+                                                    obs_format=obs_format, action_format=action_format, _extra_maps=own))
         self.device = self.envs[0].device
         self.reward_weight = reward_weight
 

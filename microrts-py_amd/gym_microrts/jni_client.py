@@ -95,7 +95,10 @@ class GameClient:
 
 class JNIGridnetVecClient:
     def __init__(self, num_selfplay_envs, num_bot_envs, max_steps, rfs, microrts_path, map_paths, ai2s, utt=None,
-                 partial_obs=False, device=None):
+                 partial_obs=False, device=None, action_format="dense"):
+        if action_format != "dense":
+            raise ValueError("JNIGridnetVecClient keeps the Java client's gameStep(action rows): "
+                             f"action_format={action_format!r} is not available here (use MicroRTSGridModeVecEnv)")
         if device is None:
             if not torch.cuda.is_available():
                 raise _native.MicroRTSError("JNIGridnetVecClient needs a GPU (HIP) device: the engine has no CPU fallback")

@@ -24,6 +24,13 @@ bytes a row against 316).  `sample` and `evaluate` take it in place of `mask` wi
     mask, source = policy_head.unpack_masks(packed)
     actions, logprob, entropy = policy_head.sample(logits, packed, seed=s, step=t)
     logprob, entropy = policy_head.evaluate(logits, packed, actions=actions)
+
+Packed actions: a row's seven components in one int32 word per cell, [N, HW]
+(gym_microrts.packed_actions; 4 bytes a cell against 56).  `sample(..., action_format="packed")`
+writes them -- what an `action_format="packed"` env's step() takes zero-copy -- and
+`evaluate` recognises them by dtype int32 and N*HW elements.  With either mask format the
+results are the dense-action calls' bit for bit: log-prob, entropy, gradient, and
+`packed_actions.unpack_actions` of the words.
 """
 import ctypes
 
@@ -109,9 +116,13 @@ def _inputs(logits, mask, source, float_masks, actions=None):
     if tuple(logits.shape) not in ((n * hw, CHANNELS), (n, hw, CHANNELS)):
         raise ValueError(f"logits must be [N*HW, {CHANNELS}] or [N, HW, {CHANNELS}] with N, HW = {(n, hw)}, not {tuple(logits.shape)}")
     if actions is not None:
-        _need(actions, "actions", (torch.int64,))
-        if actions.numel() != n * hw * COMPONENTS:
-            raise ValueError(f"actions must hold N*HW*{COMPONENTS} = {n * hw * COMPONENTS} elements, not {tuple(actions.shape)}")
+        # packed action words: int32 with N*HW elements; anything else is held to the int64 rows' rules
+        words = isinstance(actions, torch.Tensor) and actions.dtype == torch.int32 and actions.numel() == n * hw
+        if not words:
+            _need(actions, "actions", (torch.int64,))
+            if actions.numel() != n * hw * COMPONENTS:
+                raise ValueError(f"actions must hold N*HW*{COMPONENTS} = {n * hw * COMPONENTS} elements (int64 rows; or N*HW = {n * hw} "
+                                 f"packed int32 words), not {tuple(actions.shape)}")
         tensors["actions"] = actions
     _on_gpu(logits, **tensors)
     return logits.contiguous(), _as_int32(mask), None if source is None else _as_int32(source), n, hw
@@ -121,16 +132,16 @@ def _stream(dev):
     return torch.cuda.current_stream(dev).cuda_stream
 
 
-def _head(name, logits, mask, source, *tail):
-    """Call the action head's entry point mrts_`name` (dense) or mrts_`name`_packed (source is
-    None) on the logits' device and current stream."""
+def _head(name, logits, mask, source, n, hw, head, actions, *tail):
+    """Call the action head's entry point mrts_`name`_fmt on the logits' device and current
+    stream: packed masks when source is None, packed action words when `actions` is int32.
+    `head`: the arguments between the shape and the actions."""
     dev = logits.device
-    if source is None:
-        name, masks = name + "_packed", (mask.data_ptr(),)
-    else:
-        masks = (mask.data_ptr(), source.data_ptr())
+    mfmt, src = (_native.MRTS_MASK_PACKED, None) if source is None else (_native.MRTS_MASK_DENSE, source.data_ptr())
+    afmt = _native.MRTS_ACT_PACKED if actions.dtype == torch.int32 else _native.MRTS_ACT_DENSE
     with torch.cuda.device(dev):
-        rc = getattr(_native.lib(), "mrts_" + name)(_stream(dev), logits.data_ptr(), *masks, *tail)
+        rc = getattr(_native.lib(), f"mrts_{name}_fmt")(_stream(dev), logits.data_ptr(), mfmt, mask.data_ptr(), src, n, hw, *head,
+                                                       afmt, actions.data_ptr(), *tail)
     _native.check(rc, None, name)
 
 
@@ -166,21 +177,27 @@ def unpack_masks(packed):
     return mask, source
 
 
-def sample(logits, mask, source=None, *, seed, step, env0=0):
+def sample(logits, mask, source=None, *, seed, step, env0=0, action_format="dense"):
     """Draw one action per component and cell: (actions [N, HW, 7] int64, what
-    `step()` takes zero-copy; logprob [N]; entropy [N], float32).  The draw is the
+    `step()` takes zero-copy -- or, with action_format="packed", the same actions as packed
+    words [N, HW] int32, what an action_format="packed" env takes; logprob [N]; entropy [N], float32).  The draw is the
     inverse CDF of the masked softmax at the Philox words keyed by (cell, env0 + env,
     step) under `seed` -- the stream of the engine's stand-in sampler, so a shard
     [env0, env0 + N) draws exactly its slice of one larger batch.  No grad.
     `mask` with `source`: the dense tensors; `mask` alone: packed [N, HW, 3] int32."""
+    if action_format not in ("dense", "packed"):
+        raise ValueError(f"action_format must be 'dense' or 'packed', not {action_format!r}")
     _format(mask, source)
     lg, m, s, n, hw = _inputs(logits, mask, source, False)
     dev = lg.device
-    actions = torch.empty((n, hw, COMPONENTS), dtype=torch.int64, device=dev)
+    if action_format == "packed":
+        actions = torch.empty((n, hw), dtype=torch.int32, device=dev)
+    else:
+        actions = torch.empty((n, hw, COMPONENTS), dtype=torch.int64, device=dev)
     logprob = torch.empty((n,), dtype=torch.float32, device=dev)
     entropy = torch.empty((n,), dtype=torch.float32, device=dev)
-    _head("policy_sample", lg.detach(), m, s, n, hw, int(env0), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(step) & 0xFFFFFFFF,
-          actions.data_ptr(), logprob.data_ptr(), entropy.data_ptr())
+    _head("policy_sample", lg.detach(), m, s, n, hw, (int(env0), ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), int(step) & 0xFFFFFFFF),
+          actions, logprob.data_ptr(), entropy.data_ptr())
     return actions, logprob, entropy
 
 
@@ -191,7 +208,7 @@ class _Evaluate(torch.autograd.Function):
     def forward(ctx, logits, mask, source, actions, n, hw):
         logprob = torch.empty((n,), dtype=torch.float32, device=logits.device)
         entropy = torch.empty((n,), dtype=torch.float32, device=logits.device)
-        _head("policy_evaluate", logits, mask, source, n, hw, actions.data_ptr(), logprob.data_ptr(), entropy.data_ptr())
+        _head("policy_evaluate", logits, mask, source, n, hw, (), actions, logprob.data_ptr(), entropy.data_ptr())
         ctx.save_for_backward(logits, mask, source, actions)
         ctx.shape = (n, hw)
         return logprob, entropy
@@ -206,13 +223,14 @@ class _Evaluate(torch.autograd.Function):
         g_lp = zero if g_lp is None else g_lp.to(torch.float32).contiguous()
         g_ent = zero if g_ent is None else g_ent.to(torch.float32).contiguous()
         grad = torch.empty_like(logits)   # the kernel writes every element
-        _head("policy_evaluate_backward", logits, mask, source, n, hw, actions.data_ptr(), g_lp.data_ptr(), g_ent.data_ptr(),
+        _head("policy_evaluate_backward", logits, mask, source, n, hw, (), actions, g_lp.data_ptr(), g_ent.data_ptr(),
               grad.data_ptr())
         return grad, None, None, None, None, None
 
 
 def evaluate(logits, mask, source=None, actions=None):
-    """(logprob [N], entropy [N]) of `actions` ([N, HW, 7] or [N, HW*7] int64) under the
+    """(logprob [N], entropy [N]) of `actions` ([N, HW, 7] or [N, HW*7] int64, or packed action
+    words: int32 with N*HW elements, read as the rows they stand for) under the
     masked softmax; differentiable in `logits` (the backward is a kernel too).  `mask` /
     `source` may also be the float32 copies a rollout buffer holds: they are converted
     to int32 once per call.  An action the mask forbids contributes -1e8, the
