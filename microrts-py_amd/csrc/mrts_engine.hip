@@ -301,13 +301,30 @@ __device__ __forceinline__ void bot_setup_workgroup(const EngineParams& p, const
     }
 }
 
+// A wave-uniform flag as one scalar word, tested where it is used.  (A bool that lives across phases is kept as
+// a 64-bit lane mask, two scalar registers, and the step kernel sits at its scalar-register limit; the empty
+// asm keeps the compiler from merging the tests of one word into such a mask again.)
+__device__ __forceinline__ int flag_word(int b) {
+    b = __builtin_amdgcn_readfirstlane(b);
+    asm volatile("" : "+s"(b));
+    return b;
+}
+// The full-workgroup step (k_step's FULL: every engine of the launch has HW == NT, one cell per lane and no lane
+// idle -- 16x16 on 256 lanes): HW is a compile-time constant from here to the next barrier.  The cell loops run
+// once without a bound check, the wider paths drop out, and the LDS arrays' offsets fold into the instructions.
+// Loads of p.HW behind a barrier are new loads: say it again there.
+template <bool FULL, int NT>
+__device__ __forceinline__ void full_hw(const EngineParams& p) {
+    if (FULL) __builtin_assume(p.HW == NT);
+}
+
 struct Game {
     int g, env0, nviews, selfplay;
 };
 __device__ __forceinline__ Game game_of(const EngineParams& p, int g) {
     Game G;
     G.g = g;
-    G.selfplay = g < p.nsp_games;
+    G.selfplay = flag_word(g < p.nsp_games);
     G.env0 = G.selfplay ? 2 * g : p.nsp + (g - p.nsp_games);
     G.nviews = G.selfplay ? 2 : 1;
     return G;
@@ -635,11 +652,13 @@ __device__ __forceinline__ void stream_masks_delta(const EngineParams& p, const 
 // `odelta` (k_step with EngineParams::obs_delta): L.outw[0, HW) arrives holding the cells' keys
 // (obs_key) in the loaded state, written by the lanes that own the cells in phase A or, on the
 // early path, ahead of a barrier; only the rows of cells whose key changed are stored (stream_obs_delta).
-template <int NT, int P, typename OT>
+// `deltas`: bit 0 `delta`, bit 1 `odelta`, as one flag word (flag_word) that each phase tests for itself.
+template <int NT, int P, typename OT, bool FULL = false>
 __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L, const Game& G, bool obs, bool masks, int res0,
-                                             int res1, int skip = 0, int* early_cnt = nullptr, bool delta = false,
-                                             bool odelta = false) {
+                                             int res1, int skip = 0, int* early_cnt = nullptr, int deltas = 0) {
+    full_hw<FULL, NT>(p);
     const int HW = p.HW;
+    const bool delta = (deltas & 1) != 0;
     if (skip == 0 && obs && masks) {
         const int nw = vis_words(HW);
         for (int c = threadIdx.x; c < HW; c += NT) mask_words(p, L, G, c, res0, res1, delta);
@@ -648,8 +667,10 @@ __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L
         __syncthreads();
         MRTS_STAMP(8, threadIdx.x == 0);
         __builtin_amdgcn_s_setprio(0);
-        if (delta) stream_masks_delta(p, L, G, threadIdx.x, NT);
+        full_hw<FULL, NT>(p);
+        if (flag_word(deltas) & 1) stream_masks_delta(p, L, G, threadIdx.x, NT);
         else stream_masks(p, L, G, threadIdx.x, NT);
+        const bool odelta = (flag_word(deltas) & 2) != 0;
         if (P == 31) {   // compute_vis's sight disks (cleared above)
             for (int c = threadIdx.x; c < HW; c += NT) {
                 const uint32_t u = L.unit[c];
@@ -660,11 +681,14 @@ __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L
         }
         for (int c = threadIdx.x; c < HW; c += NT) onehot_words<P>(p, L, G, c, odelta);
         __syncthreads();
+        full_hw<FULL, NT>(p);
         stream_obs_kind<P, OT>(p, L, G, threadIdx.x, NT, odelta);
         MRTS_STAMP_MAX(9, (threadIdx.x & 63) == 0);
         return;
     }
     if (obs && P == 31) compute_vis<NT>(p, L);
+    full_hw<FULL, NT>(p);
+    const bool odelta = (flag_word(deltas) & 2) != 0;
     const int a0 = early_cnt ? skip : 0;   // phase A's first lane
     for (int c = (int)threadIdx.x - a0; c < HW; c += NT - a0) {
         if (obs) onehot_words<P>(p, L, G, c, odelta);
@@ -689,8 +713,9 @@ __device__ __forceinline__ void emit_outputs(const EngineParams& p, const Lds& L
     MRTS_STAMP(8, (int)threadIdx.x == skip);
     __builtin_amdgcn_s_setprio(0);
     const int t0 = (int)threadIdx.x - skip, nt = NT - skip;
-    if (obs) stream_obs_kind<P, OT>(p, L, G, t0, nt, odelta);
-    if (masks && delta) stream_masks_delta(p, L, G, t0, nt);
+    full_hw<FULL, NT>(p);
+    if (obs) stream_obs_kind<P, OT>(p, L, G, t0, nt, (flag_word(deltas) & 2) != 0);
+    if (masks && (flag_word(deltas) & 1)) stream_masks_delta(p, L, G, t0, nt);
     else if (masks) stream_masks(p, L, G, t0, nt);
     MRTS_STAMP_MAX(9, (threadIdx.x & 63) == 0);
 }
@@ -1211,14 +1236,17 @@ __device__ __forceinline__ void commit_game(const EngineParams& p, const Lds& L,
     __syncthreads();
 }
 
-// One game per workgroup (a persistent variant looping over games measured
-// slower: hipcc allocates 164 VGPRs for the looped body).
+// One game per workgroup.  A persistent variant looping over games measured slower, and still does not
+// fit: hipcc allocates 153 VGPRs (3 waves / SIMD) for the looped general body and 115 (4 waves) for the
+// looped full-workgroup one, against 68 and 55 for one game per workgroup (profiles/step_chain/README.md).
+// FULL: HW == NT for every engine of the launch (full_hw).
 // FB (bot fusion, p.fuse_bots): in a bot game's workgroup, wave 0 decides the
 // NEXT tick's bot actions (bots::bot_game on the state just stored) while waves
 // 1.. stream this tick's outputs; the workgroup's LDS is then the fused layout (fused_carve).
-template <int NT, int P, typename OT, bool FB>
+template <int NT, int P, typename OT, bool FB, bool FULL>
 __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    full_hw<FULL, NT>(p);
     const int HW = p.HW;
     const bool early_layout = FB && P == 29 && p.early_bot;
     const bool botg = FB && g >= p.nsp_games && NT > 64;   // the workgroup runs the next tick's bot
@@ -1285,12 +1313,12 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     // delta obs: the keys (obs_key) of this lane's cells in the state just loaded -- of what the obs buffer
     // holds -- kept in registers until the tick is over (at most MRTS_OBS_DELTA_CELLS cells per lane:
     // mrts_capi.cpp obs_delta_ok)
-    bool odelta = false;
+    int odelta_w = 0;   // (a flag word: flag_word)
     constexpr int KB = OBS_KEY_BITS, KPR = 32 / KB;   // bits per key, keys per register
     uint32_t okey[MRTS_OBS_DELTA_CELLS / KPR] = {};
     if constexpr (!obs_packed<OT> && obs_delta_built<P>) {
-        odelta = p.obs_delta != 0;
-        if (odelta) {
+        odelta_w = flag_word(p.obs_delta);
+        if (odelta_w) {
 #pragma unroll
             for (int k = 0; k < MRTS_OBS_DELTA_CELLS; k++) {
                 const int c = (int)threadIdx.x + k * NT;
@@ -1626,6 +1654,7 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     }
     // (no barrier: the rewards read only SC_R0.. words, which the reset leaves
     // alone, and nothing above reads the cell arrays it rewrites)
+    full_hw<FULL, NT>(p);
     if (reset) {
         reset_into_lds<NT>(p, L, map_now);
         if (threadIdx.x == 0) {
@@ -1638,6 +1667,7 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     __syncthreads();
     // (7) write back + one-hot observation of every view
     MRTS_STAMP(7, threadIdx.x == 0);
+    full_hw<FULL, NT>(p);
     store_game<NT>(p, L, g);
     const int res0 = L.sc[SC_RES0], res1 = L.sc[SC_RES1];   // before the early bot may reuse the scalars' bytes
     // + getMasks of the next tick (bound mask outputs): every read of this
@@ -1656,8 +1686,9 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     // source rows) are marked in the mask words' region -- dead scratch lists, or a bot
     // game's own region -- by the lane that met the cell in the decode; phase A reads the
     // mark back on the same lane, or, on the early path, behind the barriers below.
-    const bool delta = p.mask != nullptr && p.mask_delta != 0;
-    if (delta)
+    const int deltas = flag_word((p.mask != nullptr && p.mask_delta != 0 ? 1 : 0) | (odelta_w ? 2 : 0));   // emit_outputs' flag word
+    const bool odelta = (deltas & 2) != 0;
+    if (deltas & 1)
         for (int c = threadIdx.x, k = 0; c < HW; c += NT, k++)
             for (int v = 0; v < G.nviews; v++) L.outm[3 * (v * HW + c) + 2] = ((was_src >> (2 * k + v)) & 1u) ? MASK_ROW_STORE : 0u;
     // Delta obs: each lane leaves its cells' old keys where phase A writes the new one-hot words (L.outw:
@@ -1682,8 +1713,8 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
         MRTS_STAMP(14, threadIdx.x == 0);
     }
     if (!early || threadIdx.x >= 64)
-        emit_outputs<NT, P, OT>(p, L, G, true, p.mask != nullptr, res0, res1, botg ? 64 : 0, early ? F.early_cnt : nullptr, delta,
-                                odelta);
+        emit_outputs<NT, P, OT, FULL>(p, L, G, true, p.mask != nullptr, res0, res1, botg ? 64 : 0, early ? F.early_cnt : nullptr,
+                                      deltas);
     if (FB && botg && threadIdx.x < 64) {
         if (early) __builtin_amdgcn_s_setprio(3);   // the latency-bound bot wave first; the streaming waves are memory-bound
         bots::bot_game<true>(p, g - p.nsp_games, 1, F.B, L.sc, pf_ok, pf.aa, pf.aa2, early);
@@ -1697,12 +1728,15 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
 // most 2 * MRTS_STEP_GROUP_MAX entries) and runs that engine's game.  Each
 // engine's arrays, map size and LDS carve are its own; the launch's dynamic LDS
 // is the largest member's.  A single engine is a one-member, one-segment group.
-template <int NT, int P, typename OT, bool FB = false>
+// FULL: every member has HW == NT (full_hw; the launch checks), which brings the kernel to 8 waves per SIMD -- 8
+// resident games per CU, 2048 of the headline's 4096, two rounds instead of 2.29 -- with no occupancy hint: asking
+// for 8 waves (amdgpu_waves_per_eu) also cuts the scalar registers to 80 and the kernel then spills three of them.
+template <int NT, int P, typename OT, bool FB = false, bool FULL = false>
 __global__ __launch_bounds__(NT) void k_step(const StepGroup sg) {
     const int b = blockIdx.x;
     int k = 0;
     while (k + 1 < sg.nseg && b >= sg.seg_block[k + 1]) k++;
-    step_game<NT, P, OT, FB>(sg.e[sg.seg_member[k]], sg.seg_game[k] + (b - sg.seg_block[k]));
+    step_game<NT, P, OT, FB, FULL>(sg.e[sg.seg_member[k]], sg.seg_game[k] + (b - sg.seg_block[k]));
 }
 
 // ---------------------------------------------------------------------------
@@ -1788,11 +1822,18 @@ static auto with_obs(bool partial, int kind, F&& f) {
 // The step kernel of a launch's (planes, obs type, bot fusion).  No 64-lane launch
 // is fused (step_nt: the fused step needs a wave besides the bot's), so no fused
 // 64-lane kernel is built.
+// full: every member has HW == NT; built for the unfused 256-lane step (16x16), the flagship's.
 template <int NT>
-static void launch_step(const StepGroup& sg, int grid, size_t sh, hipStream_t s, bool partial, int kind, bool fb) {
+static void launch_step(const StepGroup& sg, int grid, size_t sh, hipStream_t s, bool partial, int kind, bool fb, bool full) {
     with_obs(partial, kind, [&](auto planes, auto ot) {
         constexpr int P = decltype(planes)::value;
         using OT = decltype(ot);
+        if constexpr (NT == 256) {
+            if (!fb && full) {
+                hipLaunchKernelGGL((k_step<NT, P, OT, false, true>), dim3(grid), dim3(NT), sh, s, sg);
+                return;
+            }
+        }
         if (!fb) hipLaunchKernelGGL((k_step<NT, P, OT>), dim3(grid), dim3(NT), sh, s, sg);
         else if constexpr (NT > 64) hipLaunchKernelGGL((k_step<NT, P, OT, true>), dim3(grid), dim3(NT), sh, s, sg);
     });
@@ -1855,7 +1896,9 @@ static hipError_t step_group(const EngineParams* ps, int n, hipStream_t s, bool 
         }
     sg.seg_block[sg.nseg] = grid;
     if (grid == 0) return hipSuccess;
-    with_nt(NT, [&](auto nt) { launch_step<decltype(nt)::value>(sg, grid, sh, s, p0.partial_obs, p0.obs_kind, fused); });
+    bool full = true;
+    for (int i = 0; i < n; i++) full = full && sg.e[i].HW == NT;
+    with_nt(NT, [&](auto nt) { launch_step<decltype(nt)::value>(sg, grid, sh, s, p0.partial_obs, p0.obs_kind, fused, full); });
     return hipGetLastError();
 }
 
