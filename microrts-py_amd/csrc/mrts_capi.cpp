@@ -242,7 +242,7 @@ static void masks_written(mrts_vec *h, hipError_t e, bool dense) {
 // delta needs a bit per cell and view in one register of the lane that owns the cell: at
 // most 16 cells per lane of the narrowest step workgroup (every map mrts_create accepts)
 static bool delta_ok(const mrts_vec *h) {
-    return h->mask_delta && h->masks_synced && h->next_mask && h->HW <= 16 * mrts_engine_step_layout(h->HW, h->W, 0, 0, 0).NT;
+    return h->mask_delta && h->masks_synced && h->next_mask && h->HW <= MRTS_MASK_DELTA_CELLS * mrts_engine_step_layout(h->HW, h->W, 0, 0, 0).NT;
 }
 
 // the launches that write obs report here: `dense` = every game's rows, into `obs`

@@ -99,6 +99,10 @@ __host__ __device__ inline int vis_words(int HW) { return HW / 32 + 1; }   // on
 // registers through the tick (mrts_engine.hip obs_key), for at most this many cells per lane: every
 // prefetched size
 #define MRTS_OBS_DELTA_CELLS 4
+// delta masks (EngineParams::mask_delta): a lane keeps two bits per cell (which views held a source row there in
+// the loaded state) in one register through the tick (mrts_engine.hip LaneRec::was_src), for at most this many
+// cells per lane
+#define MRTS_MASK_DELTA_CELLS 16
 struct EngineParams {
     int4 *cells;            // [G][cstride] (the first HW records of each game's row)
     int cstride;            // int4 records between consecutive games' cells (>= HW)

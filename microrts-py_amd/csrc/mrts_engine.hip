@@ -1236,6 +1236,335 @@ __device__ __forceinline__ void commit_game(const EngineParams& p, const Lds& L,
     __syncthreads();
 }
 
+// ---------------------------------------------------------------------------
+// The tick behind the decode, phase by phase (step_game below holds the load and the decode, then the list).
+// Barriers: each phase is ordered after the last one that wrote what it reads from OTHER lanes; a phase that
+// reads only its own lane's cells (the same c = threadIdx.x + k * NT walk) follows its predecessor without
+// one.  Each phase's header says what it reads from other lanes, what it writes, which barrier it relies on
+// and whether it ends with one.
+
+// What the phases share.  Passed by reference; it dissolves when the phases are inlined.
+struct Tick {
+    const EngineParams& p;
+    const Lds& L;
+    const Grid gd;   // (gd.HW is the HW that full_hw made a constant at the kernel's start)
+    const int g;
+    Game G;
+    int posw;        // words of one half of L.claim (pos_words)
+    int time;        // of the loaded state
+    bool bot0;       // bot-vs-bot game (MicroRTSBotVecEnv): player 0's PlayerAction comes from k_bot too
+    int npa, npa0;   // entries of the device bots' PlayerActions (player 1 / player 0)
+};
+// What a lane keeps of its own cells from one phase to a later one.
+constexpr int OKEY_PER_REG = 32 / OBS_KEY_BITS;
+struct LaneRec {
+    int4 aa, aa2;     // carried for write_back only: the bot wave's prefetched abstract-action words (StatePf::aa)
+    // delta masks: bit 2 k + v = this lane's k-th cell was a source row of view v in the loaded state
+    // (cell_mask's first test), i.e. the bound mask buffer holds a row there (mrts_capi.cpp delta_ok)
+    uint32_t was_src;
+    // delta obs: the keys (obs_key) of this lane's cells in the loaded state -- of what the obs buffer holds
+    // (at most MRTS_OBS_DELTA_CELLS cells per lane: mrts_capi.cpp obs_delta_ok)
+    uint32_t okey[MRTS_OBS_DELTA_CELLS / OKEY_PER_REG];
+};
+
+// delta obs: each lane leaves its cells' old keys where phase A writes the new one-hot words (L.outw)
+template <int NT>
+__device__ __forceinline__ void old_keys(const Tick& S, const LaneRec& R) {
+    constexpr int KB = OBS_KEY_BITS, KPR = OKEY_PER_REG;
+#pragma unroll
+    for (int k = 0; k < MRTS_OBS_DELTA_CELLS; k++) {
+        const int c = (int)threadIdx.x + k * NT;
+        if (c < S.gd.HW) S.L.outw[c] = (R.okey[k / KPR] >> (k % KPR * KB)) & ((1u << KB) - 1u);
+    }
+}
+
+// (2a) Rows that interact with nothing else this tick issue lane-parallel: a row (agent or device bot) whose
+// target position, if a move or produce, no other row (either player) and no pending assignment claims, while
+// no pending produce is over its owner's budget (`over`, which would make every new action inconsistent); a
+// produce besides only while all of its player's produce rows this tick together with the player's dearest
+// pending produce fit the player's resources (SC_PSUM + SC_PMAX): then no prefix of the PlayerAction's
+// ResourceUsage exceeds them (fromVectorAction keeps it and every later row) and no pair of produces is over
+// budget (issue() finds no candidate for it, nor does any later row find it).  Such a row meets no candidate in
+// issue() and no other row in fromVectorAction's filter, and no ordered row of either player meets it, so
+// issuing it out of order is exact: its LinkedHashMap rank is still its cell (agent rows) or its position in
+// the bot's PlayerAction.  (A parallel produce is never a candidate of an ordered row, so it stays out of
+// L.prod.)  Everything else takes the ordered path (2b).
+// Reads from other lanes: L.claim, L.resv at the row's target, SC_PSUM / SC_PMAX, the resources.  Writes: its
+// own cells' act / seq / aux, L.resv at a target only this row claims, the reward counters (atomics), SC_NLEFT.
+// Relies on the decode's barrier.  Ends with one: these issues come before the ordered part.
+template <int NT>
+__device__ __forceinline__ void issue_parallel(const Tick& S, bool over) {
+    const EngineParams& p = S.p;
+    const Lds& L = S.L;
+    const Grid& gd = S.gd;
+    if (!over) {
+        int left = 0;   // this lane's rows left to (2b)
+        for (int c = threadIdx.x; c < gd.HW; c += NT) {
+            const uint32_t nw = L.aux[c];
+            if (!(nw & CAND)) continue;
+            const uint32_t u = L.unit[c];
+            const int q = u_owner(u);
+            const bool botrow = !S.G.selfplay && (q != 0 || S.bot0);
+            const int rank = botrow ? (int)((nw >> 12) & 0xFFFu) : c;
+            const int code = (int)(nw & 0xFFFu), ty = code_type(code);
+            if (ty == A_PRODUCE && L.sc[SC_PSUM + q] + L.sc[SC_PMAX + q] > res_of(L, q)) { left++; continue; }
+            int n = -1;
+            if (ty == A_MOVE || ty == A_PRODUCE) {
+                const int b = unchecked_pos(gd, c, code_param(code)) + p.W;
+                n = nb_cell(gd, c, code_param(code));
+                if (((L.claim[S.posw + (b >> 5)] >> (b & 31)) & 1u) || (n >= 0 && L.resv[n] >= 0)) { left++; continue; }
+            }
+            int cur = code, dur = 0;
+            if (ty == A_NONE) dur = code_param(code);
+            else if (!(nw & LEGAL)) { dur = eta_code(code, u_type(u)); cur = code_make(A_NONE, 0, 0); }
+            const int ct = code_type(cur);
+            L.act[c] = act_make(cur, ct == A_NONE ? S.time + dur : S.time + eta_code(cur, u_type(u)));
+            L.seq[c] = seq_make(S.time, q, rank);
+            if (ct == A_MOVE || ct == A_PRODUCE) L.resv[n] = c;
+            if (ct == A_HARVEST || ct == A_RETURN) atomicAdd(&L.sc[SC_R0 + 6 * q + 1], 1);
+            if (ct == A_ATTACK) atomicAdd(&L.sc[SC_R0 + 6 * q + 4], 1);
+            if (ct == A_PRODUCE) {   // ai.reward.ProduceWorker / ProduceBuilding / ProduceCombatUnit
+                const int pu = code_utype(cur);
+                atomicAdd(&L.sc[SC_R0 + 6 * q + (pu == WORKER ? 2 : (pu == BASE || pu == BARRACKS) ? 3 : 5)], 1);
+            }
+            L.aux[c] = nw & ~CAND;   // issued
+        }
+        if (left) atomicAdd(&L.sc[SC_NLEFT], left);
+    }
+    __syncthreads();
+}
+
+// (2b) The ordered path for the rest, p0 then p1 (bot envs: the passive bot issues only NONEs), on lane 0:
+// the rows are listed (an ordered compaction, the ranks of agent rows being their cells) only when (2a) left
+// any -- most ticks it leaves none.  Returns the rows listed.
+// Reads from other lanes: L.aux of every cell (the compaction); lane 0 reads the whole state.  Writes:
+// L.list, L.ballot; lane 0: act / seq / resv / prod / posbits / aux, SC_NPROD, the reward counters.
+// Relies on (2a)'s barrier.  Ends with one.
+template <int NT>
+__device__ __forceinline__ int issue_ordered(const Tick& S, bool over, int nprod) {
+    const EngineParams& p = S.p;
+    const Lds& L = S.L;
+    int nrows = 0;
+    if (over || L.sc[SC_NLEFT]) nrows = compact_cells<NT>(S.gd.HW, [&](int c) { return (L.aux[c] & CAND) != 0; }, L.list, L.ballot);
+    MRTS_STAMP(4, threadIdx.x == 0);
+    if (threadIdx.x == 0) {
+        L.sc[SC_NPROD] = nprod;
+        if (S.bot0) issue_player(p, L, S.gd, 0, L.blist0, S.npa0, false);
+        else issue_player(p, L, S.gd, 0, L.list, nrows, true);
+        if (S.G.selfplay) issue_player(p, L, S.gd, 1, L.list, nrows, true);
+        else if (S.npa > 0) issue_player(p, L, S.gd, 1, L.blist, S.npa, false);
+    }
+    __syncthreads();
+    MRTS_STAMP(5, threadIdx.x == 0);
+    return nrows;
+}
+
+// (3) fillWithNones(gs, player, 1) for every idle unit (both players), then (4) GameState.cycle(): time++,
+// the ready assignments collected, ranked into issue order and executed -- serially on lane 0, or one lane
+// per action when the set commutes.  `nrows` goes to the rollout statistics.
+// Reads from other lanes: L.list / L.aux (the ready set's cells and sequence words), L.snap, the cells the
+// actions touch.  Writes: act / seq of its own cells, claim[0, posw) (dead since the decode's claims:
+// cleared here for the ready set's harvest-pile check), L.list / L.aux / L.snap, the cells the executed
+// actions touch, the scalars (SC_NREADY / RPROD / SERIAL / UID / HAS / TIME / TICKS / ERR, resources).
+// Relies on (2b)'s barrier; its first passes read each cell on the lane that wrote it.  Two barriers
+// inside (ready set listed; ranked).  Ends with one.
+template <int NT>
+__device__ __forceinline__ void cycle(const Tick& S, int nrows) {
+    const Lds& L = S.L;
+    const Grid& gd = S.gd;
+    const int HW = gd.HW, time = S.time;
+    for (int i = threadIdx.x; i < S.posw; i += NT) L.claim[i] = 0;
+    for (int c = threadIdx.x; c < HW; c += NT) {
+        uint32_t u = L.unit[c];
+        if (u != 0 && u_owner(u) >= 0 && L.act[c] == 0) {
+            L.act[c] = act_make(A_NONE, time + 1);
+            L.seq[c] = seq_make(time, u_owner(u), 4095);
+        }
+    }
+    const int now = time + 1;
+    for (int c = threadIdx.x; c < HW; c += NT) {
+        uint32_t a = L.act[c];
+        if (a && act_done(a) <= now && code_type(act_code(a)) == A_NONE) L.act[c] = 0;
+    }
+    // the ready cells in L.list, their sequence words in L.aux (dead since the issue),
+    // appended in any order: they are ranked by sequence word below
+    for (int c = threadIdx.x; c < HW; c += NT) {
+        const uint32_t a = L.act[c];
+        if (a != 0 && act_done(a) <= now) {
+            const int pos = atomicAdd(&L.sc[SC_NREADY], 1);
+            L.list[pos] = c;
+            L.aux[pos] = L.seq[c];
+        }
+    }
+    __syncthreads();
+    const int nready = L.sc[SC_NREADY];
+    // snapshots of the ready assignments in LinkedHashMap (issue-sequence)
+    // order: lane-parallel rank by sequence word (unique among non-NONE actions);
+    // in the same pass, unitActions.remove and whether the set commutes:
+    // independent ready sets (no attack, no two harvests of one pile) do -- every
+    // target cell is distinct (moves / produces hold reservations), resources only
+    // add up, and produced units take ids in issue order.  (Attacks on cells no
+    // other ready action touches would commute too; run in parallel that way they
+    // measured neutral at 1024 and slower at 8192 envs: DESIGN.md §5.)
+    int serial = 0, nprodr = 0;
+    for (int i = threadIdx.x; i < nready; i += NT) {
+        const int c = L.list[i];
+        const uint32_t sq = L.aux[i];
+        int rank = 0, j = 0;
+        for (; j + 4 <= nready; j += 4) {   // four sequence words per LDS read, no pointer chase
+            const uint4 v = *reinterpret_cast<const uint4*>(L.aux + j);
+            rank += (v.x < sq) + (v.y < sq) + (v.z < sq) + (v.w < sq);
+        }
+        for (; j < nready; j++) rank += L.aux[j] < sq;
+        const int code = act_code(L.act[c]), ty = code_type(code);
+        L.snap[rank] = make_int4(c, (int)L.unit[c], code, L.uid[c]);
+        L.act[c] = 0;   // unitActions.remove (each ready cell is read by its own lane only)
+        if (ty == A_ATTACK) serial = 1;
+        nprodr += ty == A_PRODUCE;
+        if (ty == A_HARVEST) {
+            const int n = nb_cell(gd, c, code_param(code));
+            if (n >= 0 && (atomicOr(&L.claim[n >> 5], 1u << (n & 31)) >> (n & 31)) & 1u) serial = 1;
+        }
+    }
+    if (nprodr) atomicAdd(&L.sc[SC_RPROD], nprodr);   // the ids the produced units take (SC_RPROD starts at 0)
+    const int uid0 = L.sc[SC_UID];   // read before lane 0 may advance it (below)
+    // (the OR over lanes through an LDS word: __syncthreads_or's static LDS would cost
+    // every workgroup 256 B)
+    if (serial) L.sc[SC_SERIAL] = 1;
+    __syncthreads();
+    serial = L.sc[SC_SERIAL];
+    MRTS_STAMP(6, threadIdx.x == 0);
+    if (serial) {
+        if (threadIdx.x == 0)
+            for (int i = 0; i < nready; i++) execute_one(L, gd, L.snap[i]);
+    } else {
+        for (int i = threadIdx.x; i < nready; i += NT) {
+            const int4 sn = L.snap[i];
+            int puid = -1;
+            if (code_type(sn.z) == A_PRODUCE) {
+                puid = uid0;
+                for (int j = 0; j < i; j++) puid += code_type(L.snap[j].z) == A_PRODUCE;
+            }
+            execute_one<true>(L, gd, sn, puid);
+        }
+    }
+    // (no barrier: the scalars below are lane 0's, SC_UID is no longer read, and the
+    // unit counts -- kept by execute_one -- are read behind the next barrier)
+    if (threadIdx.x == 0) {
+        L.sc[SC_TIME] = now;
+        L.sc[SC_TICKS]++;
+        L.sc[MRTS_G_SERIAL] += serial;      // rollout statistics (mrts_game_stats)
+        L.sc[MRTS_G_ORDERED] += nrows;
+        if (now >= MRTS_MAX_TIME) atomicOr(&L.sc[SC_ERR], MRTS_ERR_TIME_OVERFLOW);   // the executing lanes may be ORing too
+        if (!serial)
+            L.sc[SC_UID] += L.sc[SC_RPROD];
+    }
+    __syncthreads();
+}
+
+// (5) PhysicalGameState.gameover / winner: the unit counts of the decode pass, less the units attacks
+// removed, plus the produced ones (execute_one); (6) rewards / done (JNIGridnetVecClient.gameStep terminal
+// handling) and the auto-reset.  steps0 / map_now: the loaded state's, read before any lane could rewrite them.
+// Reads from other lanes: SC_HAS and the reward counters.  Writes: the reward / done outputs; on a reset
+// its own cells and lane 0's scalars, else SC_STEPS.  Relies on the cycle's barrier; no barrier between the
+// rewards and the reset (the rewards read only SC_R0.. words, which the reset leaves alone, and nothing
+// here reads the cell arrays it rewrites).  Ends with one.
+template <int NT, bool FULL>
+__device__ __forceinline__ void finish_tick(const Tick& S, int steps0, int map_now) {
+    const EngineParams& p = S.p;
+    const Lds& L = S.L;
+    const Game& G = S.G;
+    const int has = L.sc[SC_HAS];
+    const bool has0 = (has & 0xFFFF) != 0, has1 = (has >> 16) != 0;
+    const bool gameover = !(has0 && has1);
+    const int winner = (has0 && !has1) ? 0 : (has1 && !has0) ? 1 : -1;
+    const int steps = steps0 + 1;
+    const bool reset = gameover || steps >= p.max_steps;
+    if (threadIdx.x < 6 * G.nviews) {
+        int v = threadIdx.x / 6, k = threadIdx.x % 6;
+        int env = G.env0 + v;
+        double r = k == 0 ? (gameover ? (winner == v ? 1.0 : -1.0) : 0.0) : (double)L.sc[SC_R0 + 6 * v + k];
+        p.raw_reward[(size_t)env * 6 + k] = r;
+        p.done[(size_t)env * 6 + k] = (uint8_t)((gameover || (k == 0 && reset)) ? 1 : 0);
+    }
+    if (p.reward && threadIdx.x < G.nviews) {   // fused `reward @ reward_weight`, done[:, 0]
+        const int v = threadIdx.x, env = G.env0 + v;
+        double s = 0.0;
+        for (int k = 0; k < 6; k++) {
+            double r = k == 0 ? (gameover ? (winner == v ? 1.0 : -1.0) : 0.0) : (p.shaping ? (double)L.sc[SC_R0 + 6 * v + k] : 0.0);
+            s = __dadd_rn(s, __dmul_rn(r, p.rw[k]));   // no FMA contraction: numpy's sequential dot
+        }
+        p.reward[env] = s;
+        p.done0[env] = (uint8_t)(reset ? 1 : 0);
+    }
+    full_hw<FULL, NT>(p);
+    if (reset) {
+        reset_into_lds<NT>(p, L, map_now);
+        if (threadIdx.x == 0) {
+            L.sc[SC_AA_N] = L.sc[MRTS_G_AA_N0] = 0;   // ai1 / ai2.reset()
+            L.sc[MRTS_G_EPISODES]++;
+        }
+    } else if (threadIdx.x == 0) {
+        L.sc[SC_STEPS] = steps;
+    }
+    __syncthreads();
+}
+
+// (7) Write back, the delta marks, and all outputs: the one-hot observation of every view + getMasks of the
+// next tick (bound mask outputs: every read of this game's source rows is behind the barriers above); in
+// a bot-fused game wave 0 then runs the next tick's bot.
+// Early bot (P == 29, p.early_bot: full observability, and for this size the bot writes none of the arrays
+// phase A reads -- unit / act / wall stay as stored, the step's scalars and visibility words are left alone,
+// its small arrays go to the tail region): once store_game has read the arrays the bot reuses, the workgroup
+// builds the bot's setup, then wave 0 starts the next tick's bot at once while waves 1.. build the output
+// words and stream them, meeting at an LDS counter instead of a workgroup barrier.  Otherwise wave 0 helps
+// with phase A and starts the bot behind its barrier (the step's arrays are dead by then: only L.outw is read
+// on).  One bot_game call site for both: the inlined bot is most of this kernel's code.
+// Delta masks: the rows the bound buffer holds from the last tick (the loaded state's source rows, R.was_src)
+// are marked in the mask words' region -- dead scratch lists, or a bot game's own region -- by the lane that
+// met the cell in the decode; phase A reads the mark back on the same lane, or, on the early path, behind the
+// barriers below.  Delta obs: old_keys, likewise.  On the early path L.outw is the uid array, which the bot's
+// setup reads up to its inner barrier, and phase A runs on other lanes: the keys go in behind the setup (whose
+// last loop does not touch the uid array) and ahead of the barrier that follows it.
+// Reads from other lanes: the scalars (store_game, the resources); emit_outputs and the bot read the whole final
+// state.  Writes: the game's global state, L.outm / L.outw marks on its own cells, then the output words'
+// region (emit_outputs) and the bot's arrays.  Relies on finish_tick's barrier.  Early path: two barriers around
+// the bot's setup; emit_outputs has its own.  The kernel's last phase.
+template <int NT, int P, typename OT, bool FB, bool FULL>
+__device__ __forceinline__ void write_back(const Tick& S, const LaneRec& R, const FusedLds& F, int odelta_w, bool botg, bool early,
+                                           bool pf_ok) {
+    const EngineParams& p = S.p;
+    const Lds& L = S.L;
+    const Game& G = S.G;
+    const int g = S.g;
+    MRTS_STAMP(7, threadIdx.x == 0);
+    full_hw<FULL, NT>(p);
+    const int HW = S.gd.HW;
+    store_game<NT>(p, L, g);
+    const int res0 = L.sc[SC_RES0], res1 = L.sc[SC_RES1];   // before the early bot may reuse the scalars' bytes
+    const int deltas = flag_word((p.mask != nullptr && p.mask_delta != 0 ? 1 : 0) | (odelta_w ? 2 : 0));   // emit_outputs' flag word
+    const bool odelta = (deltas & 2) != 0;
+    if (deltas & 1)
+        for (int c = threadIdx.x, k = 0; c < HW; c += NT, k++)
+            for (int v = 0; v < G.nviews; v++) L.outm[3 * (v * HW + c) + 2] = ((R.was_src >> (2 * k + v)) & 1u) ? MASK_ROW_STORE : 0u;
+    if (odelta && !early) old_keys<NT>(S, R);
+    if (early) {
+        __syncthreads();
+        bot_setup_workgroup<NT>(p, F.B);
+        if (odelta) old_keys<NT>(S, R);
+        __syncthreads();
+        MRTS_STAMP(14, threadIdx.x == 0);
+    }
+    if (!early || threadIdx.x >= 64)
+        emit_outputs<NT, P, OT, FULL>(p, L, G, true, p.mask != nullptr, res0, res1, botg ? 64 : 0, early ? F.early_cnt : nullptr,
+                                      deltas);
+    if (FB && botg && threadIdx.x < 64) {
+        if (early) __builtin_amdgcn_s_setprio(3);   // the latency-bound bot wave first; the streaming waves are memory-bound
+        bots::bot_game<true>(p, g - p.nsp_games, 1, F.B, L.sc, pf_ok, R.aa, R.aa2, early);
+        MRTS_STAMP(13, threadIdx.x == 0);
+    }
+}
+
 // One game per workgroup.  A persistent variant looping over games measured slower, and still does not
 // fit: hipcc allocates 153 VGPRs (3 waves / SIMD) for the looped general body and 115 (4 waves) for the
 // looped full-workgroup one, against 68 and 55 for one game per workgroup (profiles/step_chain/README.md).
@@ -1285,10 +1614,8 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     if (early)   // the early bot's tail arrays start zeroed
         for (int i = threadIdx.x; i < F.tail_words; i += NT) F.tail[i] = 0;
     const Game G = game_of(p, g);
-    // Barriers: each phase below is ordered after the last one that wrote what it
-    // reads from OTHER lanes; a phase that reads only its own lane's cells (the
-    // same c = threadIdx.x + k * NT walk) follows its predecessor without one.
-    // Everything zeroed or initialised here is first read after commit_game's barrier.
+    // (barriers: the paragraph above the phases)  Everything zeroed or initialised here is first read after
+    // commit_game's barrier.
     if (threadIdx.x < SC_WORDS) L.sc[threadIdx.x] = 0;
     const int posw = pos_words(HW, p.W);
     for (int i = threadIdx.x; i < 2 * posw; i += NT) L.claim[i] = 0;
@@ -1310,12 +1637,10 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
         load_game<NT>(p, L, g);
     }
     MRTS_STAMP(3, threadIdx.x == 0);
-    // delta obs: the keys (obs_key) of this lane's cells in the state just loaded -- of what the obs buffer
-    // holds -- kept in registers until the tick is over (at most MRTS_OBS_DELTA_CELLS cells per lane:
-    // mrts_capi.cpp obs_delta_ok)
+    // delta obs: the keys of this lane's cells in the state just loaded (R.okey), kept until the tick is over
+    LaneRec R{};
     int odelta_w = 0;   // (a flag word: flag_word)
-    constexpr int KB = OBS_KEY_BITS, KPR = 32 / KB;   // bits per key, keys per register
-    uint32_t okey[MRTS_OBS_DELTA_CELLS / KPR] = {};
+    constexpr int KB = OBS_KEY_BITS, KPR = OKEY_PER_REG;   // bits per key, keys per register
     if constexpr (!obs_packed<OT> && obs_delta_built<P>) {
         odelta_w = flag_word(p.obs_delta);
         if (odelta_w) {
@@ -1325,7 +1650,7 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
                 if (c < HW) {
                     const uint32_t u = L.unit[c], a = L.act[c];
                     const uint8_t wl = L.wall[c];
-                    okey[k / KPR] |= obs_key(u, a, wl) << (k % KPR * KB);
+                    R.okey[k / KPR] |= obs_key(u, a, wl) << (k % KPR * KB);
                 }
             }
         }
@@ -1341,17 +1666,15 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     //   a pending produce is over its owner's budget; + the target positions the
     //   agent's move / produce rows claim (step 2a)
     int units = 0;   // player 0's units + player 1's << 16 (SC_HAS)
-    // delta masks: bit 2 k + v = this lane's k-th cell was a source row of view v in the
-    // loaded state (cell_mask's first test), i.e. the bound mask buffer holds a row there
-    // (at most 16 cells per lane: mrts_capi.cpp delta_ok)
-    uint32_t was_src = 0;
+    // (delta masks: cell_pass takes R.was_src, at most MRTS_MASK_DELTA_CELLS cells per lane: mrts_capi.cpp delta_ok)
+    static_assert(2 * MRTS_MASK_DELTA_CELLS <= 32, "was_src: two bits per cell of a lane in one word");
     // per cell (the lane's k-th): unit counts, pending reservations / produce budgets;
     // returns the view whose agent row the cell's idle unit may take (-1: none)
     auto cell_pass = [&](int c, uint32_t u, int k) {
         const int ow = u_owner(u);
         if (u != 0 && (ow == 0 || ow == 1)) units += ow ? 1 << 16 : 1;
         const uint32_t pa = L.act[c];
-        if (u != 0 && pa == 0 && ow >= 0 && ow < G.nviews) was_src |= 1u << ((2 * k + ow) & 31);
+        if (u != 0 && pa == 0 && ow >= 0 && ow < G.nviews) R.was_src |= 1u << ((2 * k + ow) & 31);
         if (pa) {
             const int code = act_code(pa), ty = code_type(code);
             if (ty == A_MOVE || ty == A_PRODUCE) {
@@ -1464,262 +1787,15 @@ __device__ __forceinline__ void step_game(const EngineParams& p, const int g) {
     // L.prod and the bot rows before everything below
     __syncthreads();
     const int nprod = L.sc[SC_NPEND];
-    // (2a) rows that interact with nothing else this tick issue lane-parallel: a
-    //      row (agent or device bot) whose target position, if a move or produce,
-    //      no other row (either player) and no pending assignment claims, while no
-    //      pending produce is over its owner's budget (which would make every new
-    //      action inconsistent); a produce besides only while all of its player's
-    //      produce rows this tick together with the player's dearest pending
-    //      produce fit the player's resources (SC_PSUM + SC_PMAX): then no prefix of
-    //      the PlayerAction's ResourceUsage exceeds them (fromVectorAction keeps it
-    //      and every later row) and no pair of produces is over budget (issue()
-    //      finds no candidate for it, nor does any later row find it).  Such a row
-    //      meets no candidate in issue() and no other row in fromVectorAction's
-    //      filter, and no ordered row of either player meets it, so issuing it out
-    //      of order is exact: its LinkedHashMap rank is still its cell (agent rows)
-    //      or its position in the bot's PlayerAction.  (A parallel produce is never
-    //      a candidate of an ordered row, so it stays out of L.prod.)  Everything
-    //      else takes the ordered path (2b).
     const bool over = L.sc[SC_OVER] != 0;
-    {
-        if (!over) {
-            int left = 0;   // this lane's rows left to (2b)
-            for (int c = threadIdx.x; c < HW; c += NT) {
-                const uint32_t nw = L.aux[c];
-                if (!(nw & CAND)) continue;
-                const uint32_t u = L.unit[c];
-                const int q = u_owner(u);
-                const bool botrow = !G.selfplay && (q != 0 || bot0);
-                const int rank = botrow ? (int)((nw >> 12) & 0xFFFu) : c;
-                const int code = (int)(nw & 0xFFFu), ty = code_type(code);
-                if (ty == A_PRODUCE && L.sc[SC_PSUM + q] + L.sc[SC_PMAX + q] > res_of(L, q)) { left++; continue; }
-                int n = -1;
-                if (ty == A_MOVE || ty == A_PRODUCE) {
-                    const int b = unchecked_pos(gd, c, code_param(code)) + p.W;
-                    n = nb_cell(gd, c, code_param(code));
-                    if (((L.claim[posw + (b >> 5)] >> (b & 31)) & 1u) || (n >= 0 && L.resv[n] >= 0)) { left++; continue; }
-                }
-                int cur = code, dur = 0;
-                if (ty == A_NONE) dur = code_param(code);
-                else if (!(nw & LEGAL)) { dur = eta_code(code, u_type(u)); cur = code_make(A_NONE, 0, 0); }
-                const int ct = code_type(cur);
-                L.act[c] = act_make(cur, ct == A_NONE ? time + dur : time + eta_code(cur, u_type(u)));
-                L.seq[c] = seq_make(time, q, rank);
-                if (ct == A_MOVE || ct == A_PRODUCE) L.resv[n] = c;
-                if (ct == A_HARVEST || ct == A_RETURN) atomicAdd(&L.sc[SC_R0 + 6 * q + 1], 1);
-                if (ct == A_ATTACK) atomicAdd(&L.sc[SC_R0 + 6 * q + 4], 1);
-                if (ct == A_PRODUCE) {   // ai.reward.ProduceWorker / ProduceBuilding / ProduceCombatUnit
-                    const int pu = code_utype(cur);
-                    atomicAdd(&L.sc[SC_R0 + 6 * q + (pu == WORKER ? 2 : (pu == BASE || pu == BARRACKS) ? 3 : 5)], 1);
-                }
-                L.aux[c] = nw & ~CAND;   // issued
-            }
-            if (left) atomicAdd(&L.sc[SC_NLEFT], left);
-        }
-    }
-    // (2b) the ordered path for the rest: listed (an ordered compaction, the ranks of
-    // agent rows being their cells) only when (2a) left any row -- most ticks it
-    // leaves none.  The barrier orders (2a)'s issues before the ordered part.
-    __syncthreads();
-    int nrows = 0;
-    if (over || L.sc[SC_NLEFT]) nrows = compact_cells<NT>(HW, [&](int c) { return (L.aux[c] & CAND) != 0; }, L.list, L.ballot);
-    MRTS_STAMP(4, threadIdx.x == 0);
-    // (2) ordered part: p0 then p1 (bot envs: the passive bot issues only NONEs)
-    if (threadIdx.x == 0) {
-        L.sc[SC_NPROD] = nprod;
-        if (bot0) issue_player(p, L, gd, 0, L.blist0, npa0, false);
-        else issue_player(p, L, gd, 0, L.list, nrows, true);
-        if (G.selfplay) issue_player(p, L, gd, 1, L.list, nrows, true);
-        else if (npa > 0) issue_player(p, L, gd, 1, L.blist, npa, false);
-    }
-    __syncthreads();
-    MRTS_STAMP(5, threadIdx.x == 0);
-    // (3) fillWithNones(gs, player, 1) for every idle unit (both players); the
-    //     cycle's first passes below read each cell on the lane that wrote it.
-    //     claim[0, posw) (dead since the decode's claims) is cleared for the ready
-    //     set's harvest-pile check.
-    for (int i = threadIdx.x; i < posw; i += NT) L.claim[i] = 0;
-    for (int c = threadIdx.x; c < HW; c += NT) {
-        uint32_t u = L.unit[c];
-        if (u != 0 && u_owner(u) >= 0 && L.act[c] == 0) {
-            L.act[c] = act_make(A_NONE, time + 1);
-            L.seq[c] = seq_make(time, u_owner(u), 4095);
-        }
-    }
-    // (4) GameState.cycle(): time++, execute ready assignments in issue order
-    const int now = time + 1;
-    for (int c = threadIdx.x; c < HW; c += NT) {
-        uint32_t a = L.act[c];
-        if (a && act_done(a) <= now && code_type(act_code(a)) == A_NONE) L.act[c] = 0;
-    }
-    // the ready cells in L.list, their sequence words in L.aux (dead since the issue),
-    // appended in any order: they are ranked by sequence word below
-    for (int c = threadIdx.x; c < HW; c += NT) {
-        const uint32_t a = L.act[c];
-        if (a != 0 && act_done(a) <= now) {
-            const int pos = atomicAdd(&L.sc[SC_NREADY], 1);
-            L.list[pos] = c;
-            L.aux[pos] = L.seq[c];
-        }
-    }
-    __syncthreads();
-    const int nready = L.sc[SC_NREADY];
-    // snapshots of the ready assignments in LinkedHashMap (issue-sequence)
-    // order: lane-parallel rank by sequence word (unique among non-NONE actions);
-    // in the same pass, unitActions.remove and whether the set commutes:
-    // independent ready sets (no attack, no two harvests of one pile) do -- every
-    // target cell is distinct (moves / produces hold reservations), resources only
-    // add up, and produced units take ids in issue order.  (Attacks on cells no
-    // other ready action touches would commute too; run in parallel that way they
-    // measured neutral at 1024 and slower at 8192 envs: DESIGN.md §5.)
-    int serial = 0, nprodr = 0;
-    for (int i = threadIdx.x; i < nready; i += NT) {
-        const int c = L.list[i];
-        const uint32_t sq = L.aux[i];
-        int rank = 0, j = 0;
-        for (; j + 4 <= nready; j += 4) {   // four sequence words per LDS read, no pointer chase
-            const uint4 v = *reinterpret_cast<const uint4*>(L.aux + j);
-            rank += (v.x < sq) + (v.y < sq) + (v.z < sq) + (v.w < sq);
-        }
-        for (; j < nready; j++) rank += L.aux[j] < sq;
-        const int code = act_code(L.act[c]), ty = code_type(code);
-        L.snap[rank] = make_int4(c, (int)L.unit[c], code, L.uid[c]);
-        L.act[c] = 0;   // unitActions.remove (each ready cell is read by its own lane only)
-        if (ty == A_ATTACK) serial = 1;
-        nprodr += ty == A_PRODUCE;
-        if (ty == A_HARVEST) {
-            const int n = nb_cell(gd, c, code_param(code));
-            if (n >= 0 && (atomicOr(&L.claim[n >> 5], 1u << (n & 31)) >> (n & 31)) & 1u) serial = 1;
-        }
-    }
-    if (nprodr) atomicAdd(&L.sc[SC_RPROD], nprodr);   // the ids the produced units take (SC_RPROD starts at 0)
-    const int uid0 = L.sc[SC_UID];   // read before lane 0 may advance it (below)
-    // (the OR over lanes through an LDS word: __syncthreads_or's static LDS would cost
-    // every workgroup 256 B)
-    if (serial) L.sc[SC_SERIAL] = 1;
-    __syncthreads();
-    serial = L.sc[SC_SERIAL];
-    MRTS_STAMP(6, threadIdx.x == 0);
-    if (serial) {
-        if (threadIdx.x == 0)
-            for (int i = 0; i < nready; i++) execute_one(L, gd, L.snap[i]);
-    } else {
-        for (int i = threadIdx.x; i < nready; i += NT) {
-            const int4 sn = L.snap[i];
-            int puid = -1;
-            if (code_type(sn.z) == A_PRODUCE) {
-                puid = uid0;
-                for (int j = 0; j < i; j++) puid += code_type(L.snap[j].z) == A_PRODUCE;
-            }
-            execute_one<true>(L, gd, sn, puid);
-        }
-    }
-    // (no barrier: the scalars below are lane 0's, SC_UID is no longer read, and the
-    // unit counts -- kept by execute_one -- are read behind the next barrier)
-    if (threadIdx.x == 0) {
-        L.sc[SC_TIME] = now;
-        L.sc[SC_TICKS]++;
-        L.sc[MRTS_G_SERIAL] += serial;      // rollout statistics (mrts_game_stats)
-        L.sc[MRTS_G_ORDERED] += nrows;
-        if (now >= MRTS_MAX_TIME) atomicOr(&L.sc[SC_ERR], MRTS_ERR_TIME_OVERFLOW);   // the executing lanes may be ORing too
-        if (!serial)
-            L.sc[SC_UID] += L.sc[SC_RPROD];
-    }
-    __syncthreads();
-    // (5) PhysicalGameState.gameover / winner: the unit counts of the decode pass,
-    //     less the units attacks removed, plus the produced ones (execute_one)
-    const int has = L.sc[SC_HAS];
-    const bool has0 = (has & 0xFFFF) != 0, has1 = (has >> 16) != 0;
-    const bool gameover = !(has0 && has1);
-    const int winner = (has0 && !has1) ? 0 : (has1 && !has0) ? 1 : -1;
-    // (6) rewards / done (JNIGridnetVecClient.gameStep terminal handling)
-    const int steps = steps0 + 1;
-    const bool reset = gameover || steps >= p.max_steps;
-    if (threadIdx.x < 6 * G.nviews) {
-        int v = threadIdx.x / 6, k = threadIdx.x % 6;
-        int env = G.env0 + v;
-        double r = k == 0 ? (gameover ? (winner == v ? 1.0 : -1.0) : 0.0) : (double)L.sc[SC_R0 + 6 * v + k];
-        p.raw_reward[(size_t)env * 6 + k] = r;
-        p.done[(size_t)env * 6 + k] = (uint8_t)((gameover || (k == 0 && reset)) ? 1 : 0);
-    }
-    if (p.reward && threadIdx.x < G.nviews) {   // fused `reward @ reward_weight`, done[:, 0]
-        const int v = threadIdx.x, env = G.env0 + v;
-        double s = 0.0;
-        for (int k = 0; k < 6; k++) {
-            double r = k == 0 ? (gameover ? (winner == v ? 1.0 : -1.0) : 0.0) : (p.shaping ? (double)L.sc[SC_R0 + 6 * v + k] : 0.0);
-            s = __dadd_rn(s, __dmul_rn(r, p.rw[k]));   // no FMA contraction: numpy's sequential dot
-        }
-        p.reward[env] = s;
-        p.done0[env] = (uint8_t)(reset ? 1 : 0);
-    }
-    // (no barrier: the rewards read only SC_R0.. words, which the reset leaves
-    // alone, and nothing above reads the cell arrays it rewrites)
-    full_hw<FULL, NT>(p);
-    if (reset) {
-        reset_into_lds<NT>(p, L, map_now);
-        if (threadIdx.x == 0) {
-            L.sc[SC_AA_N] = L.sc[MRTS_G_AA_N0] = 0;   // ai1 / ai2.reset()
-            L.sc[MRTS_G_EPISODES]++;
-        }
-    } else if (threadIdx.x == 0) {
-        L.sc[SC_STEPS] = steps;
-    }
-    __syncthreads();
-    // (7) write back + one-hot observation of every view
-    MRTS_STAMP(7, threadIdx.x == 0);
-    full_hw<FULL, NT>(p);
-    store_game<NT>(p, L, g);
-    const int res0 = L.sc[SC_RES0], res1 = L.sc[SC_RES1];   // before the early bot may reuse the scalars' bytes
-    // + getMasks of the next tick (bound mask outputs): every read of this
-    //   game's source rows (phase 1) is behind the barriers above
-    // Early bot (P == 29, p.early_bot: full observability, and for this size the bot
-    // writes none of the arrays phase A reads -- unit / act / wall stay as stored, the
-    // step's scalars and visibility words are left alone, its small arrays go to the
-    // tail region): once store_game has read the arrays the bot reuses, the workgroup
-    // builds the bot's setup, then wave 0 starts the next tick's bot at once while
-    // waves 1.. build the output words and stream them, meeting at an LDS counter
-    // instead of a workgroup barrier.  Otherwise wave 0 helps with phase A and starts
-    // the bot behind its barrier (the step's arrays are dead by then: only L.outw is
-    // read on).  One bot_game call site for both: the inlined bot is most of this
-    // kernel's code.
-    // Delta masks: the rows the bound buffer holds from the last tick (the loaded state's
-    // source rows) are marked in the mask words' region -- dead scratch lists, or a bot
-    // game's own region -- by the lane that met the cell in the decode; phase A reads the
-    // mark back on the same lane, or, on the early path, behind the barriers below.
-    const int deltas = flag_word((p.mask != nullptr && p.mask_delta != 0 ? 1 : 0) | (odelta_w ? 2 : 0));   // emit_outputs' flag word
-    const bool odelta = (deltas & 2) != 0;
-    if (deltas & 1)
-        for (int c = threadIdx.x, k = 0; c < HW; c += NT, k++)
-            for (int v = 0; v < G.nviews; v++) L.outm[3 * (v * HW + c) + 2] = ((was_src >> (2 * k + v)) & 1u) ? MASK_ROW_STORE : 0u;
-    // Delta obs: each lane leaves its cells' old keys where phase A writes the new one-hot words (L.outw:
-    // dead scratch lists, or a bot game's own region) and reads them back on the same lane.  On the early
-    // path L.outw is the uid array, which the bot's setup reads up to its inner barrier, and phase A runs
-    // on other lanes: the keys go in behind the setup (whose last loop does not touch the uid array) and
-    // ahead of the barrier that follows it.
-    auto old_keys = [&]() {
-#pragma unroll
-        for (int k = 0; k < MRTS_OBS_DELTA_CELLS; k++) {
-            const int c = (int)threadIdx.x + k * NT;
-            if (c < HW)
-                L.outw[c] = (okey[k / KPR] >> (k % KPR * KB)) & ((1u << KB) - 1u);
-        }
-    };
-    if (odelta && !early) old_keys();
-    if (early) {
-        __syncthreads();
-        bot_setup_workgroup<NT>(p, F.B);
-        if (odelta) old_keys();
-        __syncthreads();
-        MRTS_STAMP(14, threadIdx.x == 0);
-    }
-    if (!early || threadIdx.x >= 64)
-        emit_outputs<NT, P, OT, FULL>(p, L, G, true, p.mask != nullptr, res0, res1, botg ? 64 : 0, early ? F.early_cnt : nullptr,
-                                      deltas);
-    if (FB && botg && threadIdx.x < 64) {
-        if (early) __builtin_amdgcn_s_setprio(3);   // the latency-bound bot wave first; the streaming waves are memory-bound
-        bots::bot_game<true>(p, g - p.nsp_games, 1, F.B, L.sc, pf_ok, pf.aa, pf.aa2, early);
-        MRTS_STAMP(13, threadIdx.x == 0);
-    }
+    // the rest of the tick, phase by phase (above)
+    const Tick S{p, L, gd, g, G, posw, time, bot0, npa, npa0};
+    R.aa = pf.aa, R.aa2 = pf.aa2;   // (lanes < 64 of a fused bot game at one cell per lane; else never read)
+    issue_parallel<NT>(S, over);                                            // (2a)
+    const int nrows = issue_ordered<NT>(S, over, nprod);                    // (2b)
+    cycle<NT>(S, nrows);                                                    // (3) (4)
+    finish_tick<NT, FULL>(S, steps0, map_now);                              // (5) (6)
+    write_back<NT, P, OT, FB, FULL>(S, R, F, odelta_w, botg, early, pf_ok); // (7)
 }
 
 // One step launch over the games of one or more engines (map-size buckets of one

@@ -9,10 +9,11 @@ device sampler and compares, as bytes, every tick: obs, masks, source, raw rewar
 rewards and dones; the engine's error flags stay 0.  Four selfplay envs with max_steps = 24
 put auto-resets inside the run; the reward weights are non-trivial.  The shapes: 8x8 (64
 lanes), 9x13 (odd H*W, 128 lanes), 15x15 and 16x16 (one cell per lane), 24x24 (wide prefetch,
-three cells per lane), 47x24 (the unprefetched path), 16x16 under fog (31 planes, dense), 16x16
-against the device coacAI with bot fusion (the fused instantiation, early bot), an 8x8 + 16x16
-group in one launch, and the 256-lane kernel's other obs kinds: dense streams (both deltas
-off), int32 and packed obs.
+three cells per lane), 17x16 and 32x32 (the wide prefetch's boundaries: two cells per lane with a
+partly idle wave in the second pass, and exactly four), 47x24 (the unprefetched path), 16x16
+under fog (31 planes, dense), 16x16 against the device coacAI with bot fusion (the fused
+instantiation, early bot), an 8x8 + 16x16 group in one launch, and the 256-lane kernel's other
+obs kinds: dense streams (both deltas off), int32 and packed obs.
 """
 import ctypes
 import os
@@ -130,6 +131,8 @@ CASES = [("8x8",           M8,    8,  8,  [],         dict()),
          ("15x15",         M15,   15, 15, [],         dict()),
          ("16x16",         M16,   16, 16, [],         dict()),
          ("24x24_wide",    M24,   24, 24, [],         dict()),
+         ("17x16_wide2",   None,  17, 16, [],         dict()),   # two cells per lane, the second pass a quarter of one wave
+         ("32x32_wide4",   None,  32, 32, [],         dict()),   # exactly 4 x 256 cells: the last size the prefetch serves
          ("47x24_unpf",    None,  47, 24, [],         dict()),
          ("16x16_fog",     M16,   16, 16, [],         dict(partial_obs=True)),
          ("16x16_coac",    M16,   16, 16, ["coacAI"], dict(bot_fusion=True)),
