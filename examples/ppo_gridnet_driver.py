@@ -31,6 +31,10 @@ envs) runs end to end on the GPU.
   --actions packed : with --head fused, one 32-bit word per cell from the head to the step
                  (action_format="packed", gym_microrts.packed_actions): the rollout buffer keeps
                  the words -- 4 bytes a cell against 56 -- and the update evaluates from them
+  --bookkeeping device : with --api tensor, the episode statistics (VecMonitor's return / length,
+                 MicroRTSStatsRecorder's microrts_stats) and GAE run as HIP kernels
+                 (gym_microrts.rollout): no host read in the rollout loop, one drain per update;
+                 the default, host, keeps the per-step torch ops and their sync
 
 With --api numpy / hybrid the rollout makes ppo_gridnet.py's own calls in its own
 forms (`torch.Tensor(envs.reset()).to(device)`, `torch.tensor(envs.get_action_mask())
@@ -60,7 +64,7 @@ import torch.nn as nn
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "microrts-py_amd"))
 
-from gym_microrts import microrts_ai, obs_conv, packed_obs, policy_head  # noqa: E402
+from gym_microrts import microrts_ai, obs_conv, packed_obs, policy_head, rollout  # noqa: E402
 from gym_microrts.envs.vec_env import MicroRTSGridModeVecEnv  # noqa: E402
 from gym_microrts.run_driver import install as _install_compat  # noqa: E402
 
@@ -233,7 +237,7 @@ def bot_list(n):
 
 def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, updates=2, api="numpy", minibatches=4,
         epochs=2, seed=1, device="cuda", log=print, max_steps=2000, head="torch", keep_first_rollout=False, masks="dense",
-        obs="dense", encoder="torch", actions="dense"):
+        obs="dense", encoder="torch", actions="dense", bookkeeping="host"):
     """head: "torch" or "fused" (policy_fused; --api tensor only).  keep_first_rollout: the
     returned stats carry "first_rollout" -- the first rollout's buffers and the weights
     that acted in it.  masks: "dense", or "packed" (--head fused only): the rollout buffer
@@ -245,7 +249,14 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
     network takes the words and its first stage is obs_conv.encode, so nothing is unpacked.
     actions: "dense", or "packed" (--head fused only): the env takes one 32-bit word per cell, the head
     writes the words, the buffer holds them ([T, N, HW] int32, 4 bytes a cell against 56) and the update
-    gathers and evaluates from them."""
+    gathers and evaluates from them.
+    bookkeeping: "host", or "device" (--api tensor only): rollout.EpisodeStats takes step()'s tensors
+    (no host read in the rollout loop), is drained once per update into `episodes` and
+    `microrts_stats_infos`, and rollout.gae replaces the advantage loop."""
+    if bookkeeping not in ("host", "device"):
+        raise ValueError(f"bookkeeping must be 'host' or 'device', not {bookkeeping!r}")
+    if bookkeeping == "device" and api != "tensor":
+        raise ValueError("--bookkeeping device needs --api tensor: the numpy and hybrid contracts keep the host wrappers")
     if head not in ("torch", "fused"):
         raise ValueError(f"head must be 'torch' or 'fused', not {head!r}")
     if head == "fused" and api != "tensor":
@@ -267,6 +278,7 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
     if actions == "packed" and head != "fused":
         raise ValueError("--actions packed needs --head fused: only the fused head writes and reads packed actions")
     packed_a = actions == "packed"
+    on_device = bookkeeping == "device"
     packed_o = obs == "packed"
     fused_enc = encoder == "fused"
     fused = head == "fused"
@@ -329,6 +341,7 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
     next_obs = torch.Tensor(envs.reset()).to(dev) if ref_calls else obs_dev(envs.reset())   # ppo_gridnet.py:421
     next_done = torch.zeros(n, device=dev)
     ep_ret, finished = torch.zeros(n, device=dev), []
+    ep_stats = rollout.EpisodeStats.for_env(envs, 0.99) if on_device else None
     steps, t0, stats, stats_seen = 0, time.time(), {}, 0
     rollout_s = 0.0
     first_rollout = None
@@ -366,26 +379,36 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
                 obs, rew, done, infos = envs.step(a)
                 raw = infos._raw
                 next_obs, buf_rew[t], next_done = obs_dev(obs), as_dev(rew), as_dev(done)
-                ep_ret += (raw @ torch.as_tensor(envs.reward_weight, device=dev)).float()
-                if bool(next_done.any()):
-                    finished += ep_ret[next_done.bool()].tolist()
-                    ep_ret[next_done.bool()] = 0
+                if on_device:
+                    ep_stats.update(rew, done, infos)
+                else:
+                    ep_ret += (raw @ torch.as_tensor(envs.reward_weight, device=dev)).float()
+                    if bool(next_done.any()):
+                        finished += ep_ret[next_done.bool()].tolist()
+                        ep_ret[next_done.bool()] = 0
             steps += n
         torch.cuda.synchronize(dev)
         rollout_s += time.time() - tr
+        if on_device:   # ppo_gridnet.py:482-490's scan, once per update
+            records = ep_stats.drain()
+            finished += [rec["episode"]["r"] for rec in records]
+            stats_seen += sum("microrts_stats" in rec for rec in records)
         if keep_first_rollout and update == 0:
             first_rollout.update(obs=buf_obs.clone(), mask=buf_mask.clone(), actions=buf_act.clone(), logprob=buf_logp.clone(),
                                  source=buf_src.clone() if buf_src is not None else None)
         with torch.no_grad():   # GAE (gamma 0.99, lambda 0.95)
             _, last_v = net(planes_of(next_obs, dense_obs))
-            adv = torch.zeros_like(buf_rew)
-            gae = torch.zeros(n, device=dev)
-            for t in reversed(range(num_steps)):
-                nv, nd = (last_v, next_done) if t == num_steps - 1 else (buf_val[t + 1], buf_done[t + 1])
-                delta = buf_rew[t] + 0.99 * nv * (1 - nd) - buf_val[t]
-                gae = delta + 0.99 * 0.95 * (1 - nd) * gae
-                adv[t] = gae
-            ret = adv + buf_val
+            if on_device:
+                adv, ret = rollout.gae(buf_rew, buf_val, buf_done, last_v.contiguous(), next_done, 0.99, 0.95)
+            else:
+                adv = torch.zeros_like(buf_rew)
+                gae = torch.zeros(n, device=dev)
+                for t in reversed(range(num_steps)):
+                    nv, nd = (last_v, next_done) if t == num_steps - 1 else (buf_val[t + 1], buf_done[t + 1])
+                    delta = buf_rew[t] + 0.99 * nv * (1 - nd) - buf_val[t]
+                    gae = delta + 0.99 * 0.95 * (1 - nd) * gae
+                    adv[t] = gae
+                ret = adv + buf_val
         B = num_steps * n
         flat = [x.reshape((B,) + x.shape[2:]) for x in (buf_obs, buf_mask, buf_act, buf_logp, adv, ret, buf_val)]
         flat_src = buf_src.reshape(B, hw) if buf_src is not None else None
@@ -415,7 +438,7 @@ def run(num_selfplay_envs=2, num_bot_envs=0, partial_obs=False, num_steps=16, up
                  "rollout_env_steps_per_s": round(steps / rollout_s, 1), "loss": float(loss.detach()), "policy_loss": float(pg.detach()),
                  "value_loss": float(vl.detach()), "entropy": float(ent.detach().mean()), "episodes": len(finished),
                  "microrts_stats_infos": stats_seen, "api": api, "num_envs": n, "partial_obs": bool(partial_obs), "head": head,
-                 "encoder": encoder}
+                 "encoder": encoder, "bookkeeping": bookkeeping}
         log(stats)
     stats["engine_error_flags"] = base.error_flags()
     stats["finite"] = bool(np.isfinite([stats["loss"], stats["value_loss"], stats["entropy"]]).all())
@@ -439,24 +462,32 @@ SOTA = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
 
 
 def evaluate(ai="", num_steps=256, total_timesteps=1000000, agent_model_path=SOTA, agent2_model_path=SOTA, seed=1,
-             device="cuda", log=print, render=True):
+             device="cuda", log=print, render=True, bookkeeping="host", max_steps=5000):
     """experiments/ppo_gridnet_eval.py's loop over this engine: a trained GridNet (default
     the reference's agent_sota.pt) against a device bot (`ai`, 1 bot env; :60-61) or
     against a second trained GridNet in selfplay (2 selfplay envs, player 0 = agent and
     player 1 = agent2 on the even / odd envs; :62-63, 170-186), basesWorkers16x16A,
-    max_steps 5000, reward_weight [10, 1, 1, 0.2, 1, 4] (:113-123), StatsRecorder +
+    max_steps 5000 (the default), reward_weight [10, 1, 1, 0.2, 1, 4] (:113-123), StatsRecorder +
     VecMonitor (:124-125), render() every step (:161), the masks and steps in the
     script's own call forms (:168, :189-190), and one WinLoss line per finished
-    episode (:195-201).  Returns the win / loss records and the step count."""
+    episode (:195-201).  Returns the win / loss records and the step count.
+    bookkeeping="device": the env on the tensor contract without the two wrappers, rollout.EpisodeStats
+    fed every step and drained once per `num_steps`; the WinLoss lines come from its records, in the
+    same order."""
+    if bookkeeping not in ("host", "device"):
+        raise ValueError(f"bookkeeping must be 'host' or 'device', not {bookkeeping!r}")
+    on_device = bookkeeping == "device"
     torch.manual_seed(seed)
     np.random.seed(seed)
     dev = torch.device(device)
     ais = [getattr(microrts_ai, ai)] if ai else []
     nbot, nsp = (1, 0) if ai else (0, 2)
-    env = MicroRTSGridModeVecEnv(num_bot_envs=nbot, num_selfplay_envs=nsp, partial_obs=False, max_steps=5000, render_theme=2,
+    env = MicroRTSGridModeVecEnv(num_bot_envs=nbot, num_selfplay_envs=nsp, partial_obs=False, max_steps=max_steps, render_theme=2,
                                  ai2s=ais, map_paths=["maps/16x16/basesWorkers16x16A.xml"],
-                                 reward_weight=np.array([10.0, 1.0, 1.0, 0.2, 1.0, 4.0]), device=dev)
-    envs = VecMonitor(StatsRecorder(env, 0.99))
+                                 reward_weight=np.array([10.0, 1.0, 1.0, 0.2, 1.0, 4.0]), device=dev,
+                                 **(dict(return_tensors=True) if on_device else {}))
+    envs = env if on_device else VecMonitor(StatsRecorder(env, 0.99))
+    ep_stats = rollout.EpisodeStats.for_env(env, 0.99) if on_device else None
     n, hw = envs.num_envs, envs.height * envs.width
     h, w, planes = envs.observation_space.shape
     agent, agent2 = GridNet(planes, h, w).to(dev), GridNet(planes, h, w).to(dev)
@@ -466,15 +497,24 @@ def evaluate(ai="", num_steps=256, total_timesteps=1000000, agent_model_path=SOT
         agent2.load_reference_policy(load_weights(agent2_model_path))
         agent2.eval()
     num_updates = total_timesteps // (n * num_steps)
-    next_obs = torch.Tensor(envs.reset()).to(dev)
+    next_obs = envs.reset().float() if on_device else torch.Tensor(envs.reset()).to(dev)
     results, global_step = [], 0
+
+    def tally(idx, wl):
+        if ai:
+            log(f"against {ai} {wl}")
+            results.append(("agent", wl))
+        elif idx % 2 == 0:
+            log(f"player{idx % 2} {wl}")
+            results.append(("player0", wl))
+
     for _ in range(num_updates):
         for _ in range(num_steps):
             if render:
                 envs.render()
             global_step += n
             with torch.no_grad():
-                masks = torch.tensor(np.array(envs.get_action_mask())).to(dev)
+                masks = envs.get_action_mask() if on_device else torch.tensor(np.array(envs.get_action_mask())).to(dev)
                 if ai:
                     action, _, _, _ = policy(agent, next_obs, masks, hw)
                 else:
@@ -482,17 +522,19 @@ def evaluate(ai="", num_steps=256, total_timesteps=1000000, agent_model_path=SOT
                     p2, _, _, _ = policy(agent2, next_obs[1::2], masks[1::2], hw)
                     action = torch.zeros((n,) + tuple(p2.shape[1:]), dtype=torch.long, device=dev)
                     action[::2], action[1::2] = p1, p2
+            if on_device:
+                obs, rs, ds, infos = envs.step(action)
+                next_obs = obs.float()
+                ep_stats.update(rs, ds, infos)
+                continue
             obs, rs, ds, infos = envs.step(action.cpu().numpy().reshape(n, -1))
             next_obs = torch.Tensor(obs).to(dev)
             for idx, info in enumerate(infos):
                 if "episode" in info.keys():
-                    wl = float(info["microrts_stats"]["WinLossRewardFunction"])
-                    if ai:
-                        log(f"against {ai} {wl}")
-                        results.append(("agent", wl))
-                    elif idx % 2 == 0:
-                        log(f"player{idx % 2} {wl}")
-                        results.append(("player0", wl))
+                    tally(idx, float(info["microrts_stats"]["WinLossRewardFunction"]))
+        if on_device:
+            for rec in ep_stats.drain():
+                tally(rec["env"], float(rec["microrts_stats"]["WinLossRewardFunction"]))
     out = {"global_step": global_step, "results": results, "engine_error_flags": env.error_flags()}
     envs.close()
     return out
@@ -508,8 +550,10 @@ if __name__ == "__main__":
         ap.add_argument("--agent-model-path", type=str, default=SOTA)
         ap.add_argument("--agent2-model-path", type=str, default=SOTA)
         ap.add_argument("--seed", type=int, default=1)
+        ap.add_argument("--bookkeeping", choices=["host", "device"], default="host")
         a = ap.parse_args()
-        out = evaluate(a.ai, a.num_steps, a.total_timesteps, a.agent_model_path, a.agent2_model_path, a.seed)
+        out = evaluate(a.ai, a.num_steps, a.total_timesteps, a.agent_model_path, a.agent2_model_path, a.seed,
+                       bookkeeping=a.bookkeeping)
         print(json.dumps(out))
         sys.exit(0)
     ap = argparse.ArgumentParser()
@@ -526,8 +570,9 @@ if __name__ == "__main__":
     ap.add_argument("--obs", choices=["dense", "packed"], default="dense")
     ap.add_argument("--encoder", choices=["torch", "fused"], default="torch")
     ap.add_argument("--actions", choices=["dense", "packed"], default="dense")
+    ap.add_argument("--bookkeeping", choices=["host", "device"], default="host")
     a = ap.parse_args()
     out = run(a.num_selfplay_envs, a.num_bot_envs, a.partial_obs, a.num_steps, a.updates, a.api, a.minibatches,
               log=lambda s: print(json.dumps(s), flush=True), max_steps=a.max_steps, head=a.head, masks=a.masks, obs=a.obs,
-              encoder=a.encoder, actions=a.actions)
+              encoder=a.encoder, actions=a.actions, bookkeeping=a.bookkeeping)
     print(json.dumps(out))

@@ -490,6 +490,64 @@ int mrts_obs_conv_backward(void *stream, const int32_t *packed, int32_t n, int32
                            const float *weight, const float *bias, int32_t channels, const float *grad_out,
                            void *workspace, int64_t workspace_bytes, float *grad_weight, float *grad_bias);
 
+/* Episode statistics on the device, for callers of mrts_step_weighted who keep every buffer in
+ * HBM: what the reference gets from VecMonitor (ppo_gridnet.py:384-385, read at :487-488: the
+ * episode return and length) and MicroRTSStatsRecorder (ppo_gridnet.py:126-160, read at :489-490,
+ * ppo_gridnet_eval.py:200-203, league.py:278: the per-reward-function episode sums).  Stateless
+ * like the converters: the running state and the finished episodes' records live in one
+ * caller-owned device buffer `state` of the queried size, 16-byte aligned:
+ *   bytes 0..15   int64 cnt[2]: records written since init, double-buffered by the call's serial
+ *                 number -- after the calls step = s0 .. s the count is cnt[(s + 1) & 1]; 16..31 zero
+ *   then, N = num_envs elements each: ret float32[N], len int32[N], factor float64[N],
+ *   rawsum float64[6][N], disc float64[7][N]   (component-major)
+ *   then, from the next multiple of 16: the ring, float64 [capacity][MRTS_EPISODE_RECORD_DOUBLES]:
+ *   env, step, ret, len, rawsum[0..5], disc[0..6], 0.
+ * init: cnt = 0, every ret / len / rawsum / disc = 0, every factor = 1, the ring zero.
+ * update, once per env-step with that step's outputs reward [N] float64, done0 [N] bytes
+ * (non-zero = the episode ended), raw [N][6] float64, and `step`, the call's serial number
+ * (>= 0, one more than the call before; the first call's is the caller's choice).  Every operation
+ * is one IEEE round-to-nearest operation of the stated type, none fused; per env, in this order:
+ *   ret = (float)((double)ret + reward)                    numpy's float32 += float64
+ *   len = len + 1
+ *   rawsum[k] = rawsum[k] + raw[k], k = 0..5
+ *   tot = ((((raw[0] + raw[1]) + raw[2]) + raw[3]) + raw[4]) + raw[5]
+ *   disc[k] = disc[k] + factor * raw[k], k = 0..5;  disc[6] = disc[6] + factor * tot
+ *   factor = factor * gamma
+ *   if done0: append the record (env, step, (double)ret, len, rawsum, disc), then ret = len = 0,
+ *   rawsum = disc = 0, factor = 1.
+ * Record k since init goes to ring row k % capacity, and k follows the reference's scan of its
+ * infos: ascending env within a call, call order across calls -- decided by counting, not by
+ * atomics, so equal inputs give equal bytes.  A call that ends more than `capacity` episodes
+ * writes the last `capacity` of them.  Nothing runs on the host and nothing is copied.
+ * MRTS_EINVAL before any launch (the query returns it too): num_envs < 1, capacity < 1, step < 0,
+ * a null pointer, `state` not 16-byte aligned, reward / raw not 8-byte aligned.  They run on
+ * `stream`, allocate and synchronise nothing. */
+#define MRTS_EPISODE_RECORD_DOUBLES 18
+int64_t mrts_episode_stats_bytes(int32_t num_envs, int32_t capacity);
+int mrts_episode_stats_init(void *stream, void *state, int32_t num_envs, int32_t capacity);
+int mrts_episode_stats_update(void *stream, void *state, int32_t num_envs, int32_t capacity, double gamma, int64_t step,
+                              const double *reward, const uint8_t *done0, const double *raw);
+
+/* Advantages and returns of a rollout buffer in one launch (ppo_gridnet.py:496-519's loop over
+ * num_steps): rewards, values [T][N] float32, dones [T][N] and last_done [N] of done_elem
+ * (MRTS_DONE_FLOAT32: float32, what the reference stores; MRTS_DONE_UINT8: bytes, read as
+ * (float)byte), last_value [N] float32 -> advantages, returns [T][N] float32.  With
+ * g = (float)gamma, gl = (float)(gamma * lambda) (the product in double), every operation one
+ * float32 round-to-nearest operation, none fused, t = T - 1 .. 0, d_next / v_next = dones[t + 1] /
+ * values[t + 1], or last_done / last_value at t = T - 1, nnt = 1 - d_next:
+ *   MRTS_GAE_ADVANTAGES (:497-508):  delta = (r + (g * v_next) * nnt) - v,
+ *                                    A_t = delta + (gl * nnt) * A_{t+1}, A_T = 0;  returns_t = A_t + v
+ *   MRTS_GAE_RETURNS (:510-519):     R_t = r + (g * nnt) * R_{t+1}, R_T = last_value;  A_t = R_t - v.
+ * MRTS_EINVAL before any launch: T < 1, N < 1, a null pointer, another done_elem or mode, a pointer
+ * not aligned to its element.  Runs on `stream`, allocates and synchronises nothing. */
+#define MRTS_DONE_FLOAT32 0
+#define MRTS_DONE_UINT8 1
+#define MRTS_GAE_ADVANTAGES 0
+#define MRTS_GAE_RETURNS 1
+int mrts_gae(void *stream, int32_t T, int32_t N, const float *rewards, const float *values, const void *dones, int32_t done_elem,
+             const float *last_value, const void *last_done, double gamma, double lambda, int32_t mode, float *advantages,
+             float *returns);
+
 /* Per-game rollout statistics, host int32 out[num_games][MRTS_GAME_STATS]:
  * game time (ticks since the game's last reset; the reference's gs.getTime()),
  * env steps of the episode, steps since creation, and three never-reset

@@ -18,6 +18,7 @@
 #include "microrts_amd.h"
 #include "mrts_engine.h"
 #include "mrts_layout.h"
+#include "mrts_rollout.h"
 
 namespace {
 
@@ -855,6 +856,38 @@ int mrts_pack_actions(void *stream, const int64_t *actions, int64_t rows, int32_
 int mrts_unpack_actions(void *stream, const int32_t *words, int64_t rows, int64_t *actions) {
     if (!action_rows_ok(actions, words, rows)) return MRTS_EINVAL;
     return mrts_engine_unpack_actions(words, rows, actions, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+
+// Episode statistics and GAE (mrts_rollout.hip): the reference's VecMonitor + MicroRTSStatsRecorder
+// (ppo_gridnet.py:126-160, 384-385) and its advantage loop (ppo_gridnet.py:496-519) on the device.
+static bool episode_shape_ok(int32_t n, int32_t capacity) { return n >= 1 && capacity >= 1; }
+int64_t mrts_episode_stats_bytes(int32_t n, int32_t capacity) {
+    if (!episode_shape_ok(n, capacity)) return MRTS_EINVAL;
+    return mrts::rollout::layout(n, capacity).bytes;
+}
+int mrts_episode_stats_init(void *stream, void *state, int32_t n, int32_t capacity) {
+    if (!episode_shape_ok(n, capacity) || !state || !aligned16(state)) return MRTS_EINVAL;
+    return mrts_engine_episode_init(state, n, capacity, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+int mrts_episode_stats_update(void *stream, void *state, int32_t n, int32_t capacity, double gamma, int64_t step, const double *reward,
+                              const uint8_t *done0, const double *raw) {
+    if (!episode_shape_ok(n, capacity) || !state || !aligned16(state) || step < 0 || !reward || !done0 || !raw ||
+        !aligned_to(reward, 8) || !aligned_to(raw, 8))
+        return MRTS_EINVAL;
+    return mrts_engine_episode_update(state, n, capacity, gamma, step, reward, done0, raw, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
+}
+int mrts_gae(void *stream, int32_t T, int32_t N, const float *rewards, const float *values, const void *dones, int32_t done_elem,
+             const float *last_value, const void *last_done, double gamma, double lambda, int32_t mode, float *advantages,
+             float *returns) {
+    if (T < 1 || N < 1 || !rewards || !values || !dones || !last_value || !last_done || !advantages || !returns) return MRTS_EINVAL;
+    if ((done_elem != MRTS_DONE_FLOAT32 && done_elem != MRTS_DONE_UINT8) || (mode != MRTS_GAE_ADVANTAGES && mode != MRTS_GAE_RETURNS))
+        return MRTS_EINVAL;
+    const uintptr_t da = done_elem == MRTS_DONE_FLOAT32 ? 4 : 1;
+    if (!aligned_to(rewards, 4) || !aligned_to(values, 4) || !aligned_to(last_value, 4) || !aligned_to(advantages, 4) ||
+        !aligned_to(returns, 4) || !aligned_to(dones, da) || !aligned_to(last_done, da))
+        return MRTS_EINVAL;
+    return mrts_engine_gae(T, N, rewards, values, dones, done_elem == MRTS_DONE_UINT8, last_value, last_done, (float)gamma,
+                           (float)(gamma * lambda), mode, advantages, returns, (hipStream_t)stream) ? MRTS_EHIP : MRTS_OK;
 }
 
 int mrts_sample_actions_src_group(void *stream, const mrts_sample_seg *segs, int32_t nseg, uint64_t seed, uint32_t step) {

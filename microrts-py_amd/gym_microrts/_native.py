@@ -20,6 +20,9 @@ MRTS_ELEM_INT32, MRTS_ELEM_FLOAT32, MRTS_ELEM_FLOAT16, MRTS_ELEM_BFLOAT16 = 0, 1
 MRTS_ACT_DENSE, MRTS_ACT_PACKED = 0, 1
 MRTS_MASK_DENSE, MRTS_MASK_PACKED = 0, 1
 MRTS_GAME_STATS = 6
+MRTS_EPISODE_RECORD_DOUBLES = 18
+MRTS_DONE_FLOAT32, MRTS_DONE_UINT8 = 0, 1
+MRTS_GAE_ADVANTAGES, MRTS_GAE_RETURNS = 0, 1
 ERROR_NAMES = {-1: "EINVAL", -2: "EIO", -3: "EHIP", -4: "ENOTIMPL", -5: "ESTATE"}
 
 
@@ -134,6 +137,11 @@ SIGNATURES = {
     "mrts_policy_evaluate_fmt": (ctypes.c_int, [P, P, ctypes.c_int32, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32, P, P, P]),
     "mrts_policy_evaluate_backward_fmt": (ctypes.c_int, [P, P, ctypes.c_int32, P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                                          P, P, P, P]),
+    "mrts_episode_stats_bytes": (ctypes.c_int64, [ctypes.c_int32, ctypes.c_int32]),
+    "mrts_episode_stats_init": (ctypes.c_int, [P, P, ctypes.c_int32, ctypes.c_int32]),
+    "mrts_episode_stats_update": (ctypes.c_int, [P, P, ctypes.c_int32, ctypes.c_int32, ctypes.c_double, ctypes.c_int64, P, P, P]),
+    "mrts_gae": (ctypes.c_int, [P, ctypes.c_int32, ctypes.c_int32, P, P, P, ctypes.c_int32, P, P, ctypes.c_double, ctypes.c_double,
+                                ctypes.c_int32, P, P]),
     "mrts_game_stats": (ctypes.c_int, [P, P, P]),
     "mrts_bind_mask_outputs": (ctypes.c_int, [P, P, P]),
     "mrts_set_bot_fusion": (ctypes.c_int, [P, ctypes.c_int32]),
